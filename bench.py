@@ -2,6 +2,7 @@
 both AdamW updates) on the HIP path, config/conv_enc-stage1.yaml, 16 x 1 s of 16 kHz audio per GPU.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs out/    # + the last timed step's results as out/*.npy
     python bench.py --gpus 8 ...          # spawns its own ranks (torch.distributed.run, one fresh process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -48,7 +49,13 @@ def parse_args():
     ap.add_argument('--no-graph', action='store_true', help='run eagerly instead of replaying a captured hipGraph')
     ap.add_argument('--force-dp', action='store_true', help='exercise the data-parallel code path (RCCL group, eager launches, '
                                                             'segment-pipelined gradient all-reduce) even with one rank')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): every loss scalar '
+                         'of the step log and a fixed, seeded sample of the updated G and D parameters (see dump_outputs)')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return a
 
 
 def spawn_ranks_if_needed(args):
@@ -481,6 +488,53 @@ def pmc_traffic(op):
         return None
 
 
+DUMP_MAX_ELEMS = 8 << 20         # parameter sample budget of --dump-outputs: 32 MB of fp32 (the cap is 64 MB for everything)
+
+
+def dump_outputs(out_dir, log, models):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy -- the step log (one
+    float32 scalar per loss tag, `<tag>.npy`) and the parameters the step updated in place (`<model>_params_sample.npy`).
+    The parameters (G + D: ~32 M fp32) exceed the size cap, so each tensor contributes a fixed sample of its elements: all of
+    them when the model fits the budget, else a share proportional to its size (at least min(numel, 1024)), at indices drawn
+    by numpy.random.default_rng(crc32(<state_dict key>)) without replacement and sorted; tensors are concatenated in
+    named_parameters() order. Depends only on the model shapes, so two builds run with the same arguments dump the same
+    elements. The frozen stock-torch SSL extractor (`encoder.cmodel.*`) is an input of the step, not an output: left out.
+    Returns {file: shape} and the byte count for the result line."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    files, total = {}, 0
+    for tag, v in log.items():
+        a = np.asarray(float(v.detach().float().reshape(-1)[0].cpu()), dtype=np.float32)
+        np.save(os.path.join(out_dir, f'{tag}.npy'), a)
+        files[f'{tag}.npy'] = []
+        total += a.nbytes
+    named = {m: [(k, p) for k, p in mod.named_parameters() if not k.startswith('encoder.cmodel.')] for m, mod in models.items()}
+    n_all = sum(p.numel() for ps in named.values() for _, p in ps)
+    frac = min(1.0, DUMP_MAX_ELEMS / n_all)
+    for m, ps in named.items():
+        pieces = []
+        with torch.no_grad():
+            for k, p in ps:
+                n = p.numel()
+                take = n if frac >= 1.0 else min(n, max(1024, int(n * frac)))
+                flat = p.detach().reshape(-1)
+                if take == n:
+                    pieces.append(flat.float().cpu().numpy())
+                else:
+                    idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(n, take, replace=False))
+                    pieces.append(flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
+        arr = np.concatenate(pieces).astype(np.float32)
+        name = f'{m}_params_sample.npy'
+        np.save(os.path.join(out_dir, name), arr)
+        files[name] = list(arr.shape)
+        total += arr.nbytes
+    if total > 64 << 20:
+        raise SystemExit(f'--dump-outputs: {total} bytes, over the 64 MB cap')
+    return files, total
+
+
 DTYPE_EXACT = 'f32'
 DTYPE_DEFAULT = ('f32 (fp32 storage and accumulation everywhere; FiLM cond_var.2 forward and weight-grad as split-bf16 x6 products -- three exact bf16 '
                  'pieces per operand, six piece products on the bf16 MFMA, fp32 accumulate: fp32-level accuracy; every other kernel exact-fp32 MFMA)')
@@ -603,6 +657,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
     g_loss = float(log['G_loss'])
+    dumped = None
+    if rank == 0 and args.dump_outputs:      # before anything below runs the step again
+        dumped = dump_outputs(args.dump_outputs, log, dict(G=G, D=D))
     # the same K steps on the exact-fp32 kernels (split-bf16 x6 kernels off), reported beside the headline number
     fp32_ms = None
     if rank == 0 and world == 1 and not dp and not args.exact_fp32 and use_graph:
@@ -652,6 +709,12 @@ def main():
                                       'kernels they replace: 1.6e-7 / 3.5e-7 (tests/test_kernel_instances_gpu.py, 2e-5 gate); --exact-fp32 selects the latter')
         if dp_info is not None:
             out['data_parallel'] = dp_info
+        if dumped is not None:
+            out['dumped_outputs'] = dict(dir=args.dump_outputs, files=dumped[0], bytes=dumped[1],
+                                         note='inputs and weights are seeded and the gradients are summed in a fixed order: two runs of the '
+                                              'step end with the same parameter bits (measured on the conv_enc configs, '
+                                              'tests/test_determinism_gpu.py); the loss scalars are summed across blocks with float atomics '
+                                              'and may differ in their last bit')
         if ssl:
             # how much of the step is the frozen extractor (plain PyTorch-ROCm, not this repo's code)? One iteration calls it on
             # [real; corrupted] (2B signals) and, with the cycle branch, on the converted signal (B signals): model/ssl_encoder.py:141-145

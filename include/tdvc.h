@@ -204,7 +204,9 @@ typedef struct {
   float* dexc; int64_t dexc_bs;         /* [B][n_var][T], optional */
   float* dk3;                           /* [B][n_cond][3] */
   float* dw0;                           /* weight-gradient accumulator of cond_var.0, optional */
-  void* workspace; size_t workspace_bytes;   /* tdvc_film_cond0_bwd_workspace() bytes when dw0 is given */
+  void* workspace; size_t workspace_bytes;   /* tdvc_film_cond0_bwd_workspace() bytes: required when dw0 is given, else
+                                                 optional -- with it dk3 is summed in a fixed order (same bits every run),
+                                                 without it with atomics (order, and so the last bits, may vary) */
 } tdvc_film_cond0_bwd_args;
 size_t tdvc_film_cond0_bwd_workspace(int32_t B, int32_t T, int32_t n_cond, int32_t n_var);
 int tdvc_film_cond0_bwd(const tdvc_film_cond0_bwd_args* a, void* stream);
@@ -226,7 +228,8 @@ typedef struct {
   float* dexc; int64_t dexc_bs;                          /* [B][n_var][T], optional */
   float* dk3;                                            /* [B][n_cond][3] */
   float* dw0;                                            /* weight-gradient accumulator of cond_var.0, optional */
-  void* workspace; size_t workspace_bytes;               /* tdvc_film_cond_bwd_workspace() bytes when dw0 is given */
+  void* workspace; size_t workspace_bytes;               /* tdvc_film_cond_bwd_workspace() bytes: required when dw0 is
+                                                            given, else optional (as in tdvc_film_cond0_bwd_args) */
   float slope;
 } tdvc_film_cond_bwd_args;
 size_t tdvc_film_cond_bwd_workspace(int32_t B, int32_t T, int32_t n_cond, int32_t n_var);

@@ -717,53 +717,43 @@ __global__ __launch_bounds__(256, (M_REP * J >= 14 ? 3 : WGRAD_OCC)) void conv_w
 }
 
 // Row sums of the transformed dy operand -> bias gradient. One block per (channel, sample).
-__global__ __launch_bounds__(256) void conv_bias_grad_kernel(const Opnd a, int N, int Ctot, float* dbias) {
-  const int ch = blockIdx.x, b = blockIdx.y;
-  float s = 0.f;
-  const float* row = a.p + (long)b * a.bs + (long)ch * a.T;
-  const float* mrow = a.xf.aux ? a.xf.aux + (long)b * a.xf.aux_bs + (long)ch * a.T : nullptr;
+// One block per channel, the batch walked in order and the block reduced in a fixed order: the same bits every run (no
+// atomics across samples).
+__global__ __launch_bounds__(1024) void conv_bias_grad_kernel(const Opnd a, int N, int Ctot, int B, float* dbias) {
+  const int ch = blockIdx.x;
   const int kind = a.xf.kind;
-  if ((N & 3) == 0 && N == a.T && (((uintptr_t)row) & 15) == 0 && (kind <= XF_LRELU || (kind == XF_MASK_LRELU && (((uintptr_t)mrow) & 15) == 0))) {
-    // aligned rows, plain / LeakyReLU / LeakyReLU-mask prologue: float4 loads (block-uniform choice)
-    const float sl = a.xf.slope, sc = a.xf.scale;
-    for (int n = threadIdx.x * 4; n < N; n += 1024) {
-      f32x4_t v = *reinterpret_cast<const f32x4_t*>(row + n);
-      if (kind == XF_LRELU) {
+  const float sl = a.xf.slope, sc = a.xf.scale;
+  float s = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float* row = a.p + (long)b * a.bs + (long)ch * a.T;
+    const float* mrow = a.xf.aux ? a.xf.aux + (long)b * a.xf.aux_bs + (long)ch * a.T : nullptr;
+    if ((N & 3) == 0 && N == a.T && (((uintptr_t)row) & 15) == 0 && (kind <= XF_LRELU || (kind == XF_MASK_LRELU && (((uintptr_t)mrow) & 15) == 0))) {
+      // aligned rows, plain / LeakyReLU / LeakyReLU-mask prologue: float4 loads (block-uniform choice)
+      for (int n = threadIdx.x * 4; n < N; n += 4096) {
+        f32x4_t v = *reinterpret_cast<const f32x4_t*>(row + n);
+        if (kind == XF_LRELU) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = lrelu_f(v[q], sl);
-      } else if (kind == XF_MASK_LRELU) {
-        const f32x4_t m = *reinterpret_cast<const f32x4_t*>(mrow + n);
+          for (int q = 0; q < 4; ++q) v[q] = lrelu_f(v[q], sl);
+        } else if (kind == XF_MASK_LRELU) {
+          const f32x4_t m = *reinterpret_cast<const f32x4_t*>(mrow + n);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = m[q] > 0.f ? v[q] : v[q] * sl;
+          for (int q = 0; q < 4; ++q) v[q] = m[q] > 0.f ? v[q] : v[q] * sl;
+        }
+        s += ((v[0] + v[1]) + (v[2] + v[3])) * sc;
       }
-      s += ((v[0] + v[1]) + (v[2] + v[3])) * sc;
+    } else {
+      for (int n = threadIdx.x; n < N; n += 1024) s += fetch_opnd(a, b, ch, n, 0, Ctot);
     }
-  } else {
-    for (int n = threadIdx.x; n < N; n += 256) s += fetch_opnd(a, b, ch, n, 0, Ctot);
   }
-  __shared__ float sh[4];
+  __shared__ float sh[16];
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(&dbias[ch], sh[0] + sh[1] + sh[2] + sh[3]);
-}
-
-// dw[map(i)] += sum_s slab[s][i]; grid.y splits the slabs so small weights still fill the chip.
-// map: compact row-major [rows][rowlen] -> dst row stride (channel-window weights), identity otherwise.
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* slab, int nslab, long stride, long n, float* dw,
-                                                          int rowlen, long dst_row_stride, int per_y, long n_w, float* dbias) {
-  const int s0 = blockIdx.y * per_y, s1 = min(nslab, s0 + per_y);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    float s = 0.f;
-    for (int k = s0; k < s1; ++k) s += slab[(long)k * stride + i];
-    float* dstp;
-    if (i >= n_w) dstp = dbias + (i - n_w);          // trailing bias partials
-    else {
-      long dst = i;
-      if (dst_row_stride != rowlen) { const long r = i / rowlen; dst = r * dst_row_stride + (i - r * rowlen); }
-      dstp = dw + dst;
-    }
-    if (gridDim.y == 1) *dstp += s; else atomicAdd(dstp, s);
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) t += sh[w];
+    dbias[ch] += t;
   }
 }
 
@@ -776,18 +766,24 @@ struct FoldDesc {
   int nslab, rowlen, gx, gy, per_y, blk0;
 };
 constexpr int FOLD_MAX = 24;
-struct FoldBatch { FoldDesc d[FOLD_MAX]; int count, nblocks; };
+struct FoldBatch { FoldDesc d[FOLD_MAX]; int count, nblocks, partial; };
 
+// dw[map(i)] += sum_s slab[s][i]; map: compact row-major [rows][rowlen] -> dst row stride (channel-window weights), identity
+// otherwise. grid.y splits the slabs of a fold so small weights still fill the chip, without atomics: with `partial` set, only
+// split folds run and each y-block leaves its sum in its own first slab; the second launch (run_fold_batch) sums those gy
+// partials in y order. Every element is summed in a fixed order: the same bits every run.
 __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const FoldBatch fb) {
   int k = 0;
   for (int i = 1; i < fb.count; ++i)
     if ((int)blockIdx.x >= fb.d[i].blk0) k = i;
   const FoldDesc& f = fb.d[k];
+  if (fb.partial && f.gy == 1) return;
   const int lb = blockIdx.x - f.blk0, bx = lb % f.gx, by = lb / f.gx;
   const int s0 = by * f.per_y, s1 = min(f.nslab, s0 + f.per_y);
   for (long i = (long)bx * 256 + threadIdx.x; i < f.n; i += (long)f.gx * 256) {
     float s = 0.f;
     for (int q = s0; q < s1; ++q) s += f.slab[(long)q * f.stride + i];
+    if (fb.partial) { const_cast<float*>(f.slab)[(long)s0 * f.stride + i] = s; continue; }
     float* dstp;
     if (i >= f.n_w) dstp = f.dbias + (i - f.n_w);
     else {
@@ -795,7 +791,7 @@ __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const FoldBatch 
       if (f.dst_row_stride != f.rowlen) { const long r = i / f.rowlen; dst = r * f.dst_row_stride + (i - r * f.rowlen); }
       dstp = f.dw + dst;
     }
-    if (f.gy == 1) *dstp += s; else atomicAdd(dstp, s);
+    *dstp += s;
   }
 }
 
@@ -1070,14 +1066,33 @@ static int g_fold_defer = 0;
 static std::mutex g_fold_mu;
 static std::map<hipStream_t, FoldBatch>& fold_pending() { static std::map<hipStream_t, FoldBatch> m; return m; }
 
-static hipError_t fold_flush_locked(hipStream_t st) {
-  auto it = fold_pending().find(st);
-  if (it == fold_pending().end() || it->second.count == 0) return hipSuccess;
-  FoldBatch& fb = it->second;
+// Runs the folds of `fb` (consumed): split folds first leave one partial per y-block (in place, in the y-block's first slab),
+// then every fold sums its slabs -- or, when split, its gy partials -- in order.
+static hipError_t run_fold_batch(FoldBatch& fb, hipStream_t st) {
+  bool split = false;
+  for (int i = 0; i < fb.count; ++i) split = split || fb.d[i].gy > 1;
   TDVC_TRACE(slab_reduce_multi_kernel);
+  if (split) {
+    fb.partial = 1;
+    hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(fb.nblocks), dim3(256), 0, st, fb);
+    int nb = 0;
+    for (int i = 0; i < fb.count; ++i) {
+      FoldDesc& f = fb.d[i];
+      if (f.gy > 1) { f.stride *= f.per_y; f.nslab = f.gy; f.per_y = f.gy; f.gy = 1; }
+      f.blk0 = nb; nb += f.gx;
+    }
+    fb.nblocks = nb;
+  }
+  fb.partial = 0;
   hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(fb.nblocks), dim3(256), 0, st, fb);
   fb.count = 0; fb.nblocks = 0;
   return hipGetLastError();
+}
+
+static hipError_t fold_flush_locked(hipStream_t st) {
+  auto it = fold_pending().find(st);
+  if (it == fold_pending().end() || it->second.count == 0) return hipSuccess;
+  return run_fold_batch(it->second, st);
 }
 hipError_t fold_flush(hipStream_t st) { std::lock_guard<std::mutex> lk(g_fold_mu); return fold_flush_locked(st); }
 void fold_set_defer(int on) { g_fold_defer = on ? 1 : 0; }
@@ -1110,14 +1125,17 @@ hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n,
     fb.nblocks += gx * gy;
     return hipSuccess;
   }
-  TDVC_TRACE(slab_reduce_kernel);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(gx, gy), dim3(256), 0, st, slab, nslab, stride, n, dw, rowlen, dst_row_stride, per_y, n_w, dbias);
-  return hipGetLastError();
+  FoldBatch one = {};
+  FoldDesc& f = one.d[0];
+  f.slab = slab; f.dw = dw; f.dbias = dbias; f.stride = stride; f.n = n; f.dst_row_stride = dst_row_stride; f.n_w = n_w;
+  f.nslab = nslab; f.rowlen = rowlen; f.gx = gx; f.gy = gy; f.per_y = per_y; f.blk0 = 0;
+  one.count = 1; one.nblocks = gx * gy;
+  return run_fold_batch(one, st);
 }
 
 hipError_t launch_bias_grad(const Opnd& a, int N, int Ctot, int B, float* dbias, hipStream_t st) {
   TDVC_TRACE(conv_bias_grad_kernel);
-  hipLaunchKernelGGL(conv_bias_grad_kernel, dim3(Ctot, B), dim3(256), 0, st, a, N, Ctot, dbias);
+  hipLaunchKernelGGL(conv_bias_grad_kernel, dim3(Ctot), dim3(1024), 0, st, a, N, Ctot, B, dbias);
   return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 //   dW[co][ci][j] = sum_{b,t} dy'[co][t] * x'[ci][t + j*D - pad]
 // Per block: a (16*M_REP) x (16*C_REP) tile of (co, ci) for all J taps over one 256-step time chunk of one
 // sample; the 4 waves split the chunk (K-split) and are summed through LDS; partial tiles go to a slab that
-// slab_reduce_kernel folds into dW (deterministic, no atomics on the weights).
+// slab_reduce_multi_kernel folds into dW (deterministic, no atomics on the weights).
 // J (taps) and D (dilation) are template parameters and the LDS strides are constants, so every fragment
 // address in the MFMA loop is base + immediate: one vector add per step. Fragments of step s+1 are fetched
 // before the MFMAs of step s issue.

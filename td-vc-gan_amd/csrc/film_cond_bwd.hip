@@ -11,8 +11,10 @@
 //   (b) dW partial: D2[(ce,j)][c] += sum_t E'[(ce,j)][t] * d_cv0[c][t]          K (time) split over the 4 waves
 // run on v_mfma_f32_16x16x4_f32. E' carries three extra rows -- the interior mask and the two end deltas -- so the
 // dk3 sums fall out of the same matrix product (rows 24..26 of D2). dW partials stay in registers across the block's
-// chunks and go to one slab per block (folded by slab_reduce_kernel); dk3 partials are flushed with atomics when the
-// block moves to another sample.
+// chunks and go to one slab per block (folded by slab_reduce_multi_kernel); dk3 partials are written to a slot of their own when
+// the block moves to another sample (slot = block + sample: unique, since a block's samples start where the previous block's
+// end) and dk3_fold_kernel sums the slots of each sample in block order -- no atomics, the same bits every run. A caller
+// that passes no workspace (no dW wanted) gets the partials added into the zeroed dk3 with atomics instead.
 #include "conv_common.h"
 #include "api_util.h"
 
@@ -29,7 +31,8 @@ struct Cond0BwdP {
   const float* exc; long exc_bs;
   const float* w; int w_rs;            // excitation window of the weight: element [c][ce][j] at w[c * w_rs + ce * 3 + j]
   float* dexc; long dexc_bs;           // may be null
-  float* dk3;                          // [B][nc][3], zeroed before the launch
+  float* dk3;                          // [B][nc][3]: written by dk3_fold_kernel, or zeroed and accumulated with atomics
+  float* dk3_slots;                    // [nblocks + B][nc][3]: per (block, sample) partials; null = atomics
   float* slab; long slab_stride;       // may be null (no weight gradient wanted)
   int B, T, nc, ntile, tpb, nchunks;
 };
@@ -170,7 +173,8 @@ __global__ __launch_bounds__(256, 2) void film_cond0_bwd_kernel(const Cond0BwdP 
       __syncthreads();
       for (int i = tid; i < p.nc * 3; i += 256) {
         const float s = (red2[i] + red2[CB_ROWS * 3 + i]) + (red2[2 * CB_ROWS * 3 + i] + red2[3 * CB_ROWS * 3 + i]);
-        atomicAdd(p.dk3 + (long)b * p.nc * 3 + i, s);
+        if (p.dk3_slots) p.dk3_slots[((long)blockIdx.x + b) * p.nc * 3 + i] = s;
+        else atomicAdd(p.dk3 + (long)b * p.nc * 3 + i, s);
       }
     }
     b = nb; tile = ntile_i;
@@ -365,6 +369,24 @@ __global__ __launch_bounds__(256) void film_k3_multi_bwd_kernel(const float* emb
   }
 }
 
+// dk3[b][i] = sum over the blocks k that cover sample b, in order, of slot[k + b][i] (block k covers chunks [k tpb, (k+1) tpb)).
+__global__ __launch_bounds__(256) void dk3_fold_kernel(const float* slots, float* dk3, int B, int n3, int ntile, int tpb) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n3) return;
+  const int b = (int)(i / n3), e = (int)(i - (long)b * n3);
+  const int k0 = (int)(((long)b * ntile) / tpb), k1 = (int)(((long)(b + 1) * ntile - 1) / tpb);
+  float s = 0.f;
+  for (int k = k0; k <= k1; ++k) s += slots[((long)k + b) * n3 + e];
+  dk3[i] = s;
+}
+
+hipError_t launch_dk3_fold(const float* slots, float* dk3, int B, int nc, int ntile, int tpb, hipStream_t st) {
+  const long n = (long)B * nc * 3;
+  TDVC_TRACE(dk3_fold_kernel);
+  hipLaunchKernelGGL(dk3_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slots, dk3, B, nc * 3, ntile, tpb);
+  return hipGetLastError();
+}
+
 static void cond0_plan(int B, int T, int* ntile, int* tpb, int* nblocks) {
   *ntile = (T + CB_NT - 1) / CB_NT;
   const long nchunks = (long)B * (*ntile);
@@ -381,7 +403,7 @@ extern "C" size_t tdvc_film_cond0_bwd_workspace(int32_t B, int32_t T, int32_t n_
   if (B <= 0 || T <= 0 || n_cond <= 0 || n_var != 8) return 0;
   int ntile, tpb, nblocks;
   cond0_plan(B, T, &ntile, &tpb, &nblocks);
-  return (size_t)nblocks * (size_t)n_cond * 24 * sizeof(float);
+  return ((size_t)nblocks * 24 + (size_t)(nblocks + B) * 3) * (size_t)n_cond * sizeof(float);   // dW slabs + dk3 slots
 }
 
 extern "C" int tdvc_film_cond0_bwd(const tdvc_film_cond0_bwd_args* a, void* stream) {
@@ -400,17 +422,22 @@ extern "C" int tdvc_film_cond0_bwd(const tdvc_film_cond0_bwd_args* a, void* stre
   cond0_plan(a->B, a->T, &p.ntile, &p.tpb, &nblocks);
   p.nchunks = a->B * p.ntile;
   const long sstride = (long)a->n_cond * 24;
-  if (a->dw0) {
-    if (!a->workspace || a->workspace_bytes < (size_t)nblocks * sstride * sizeof(float))
-      return tdvc_fail(TDVC_EWORKSPACE, "film_cond0_bwd: workspace too small");
-    p.slab = (float*)a->workspace; p.slab_stride = sstride;
-  }
-  if (hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
+  const size_t slab_floats = a->dw0 ? (size_t)nblocks * sstride : 0, slot_floats = (size_t)(nblocks + a->B) * a->n_cond * 3;
+  // workspace: required with dw0 (slabs); without dw0 it is optional -- given, dk3 goes through per-block slots and a
+  // fixed-order fold (the same bits every run), absent, through atomics into the zeroed dk3 (summation order may vary)
+  if (a->dw0 && !a->workspace) return tdvc_fail(TDVC_EWORKSPACE, "film_cond0_bwd: workspace needed with dw0");
+  if (a->workspace && a->workspace_bytes < (slab_floats + slot_floats) * sizeof(float))
+    return tdvc_fail(TDVC_EWORKSPACE, "film_cond0_bwd: workspace too small");
+  if (a->dw0) { p.slab = (float*)a->workspace; p.slab_stride = sstride; }
+  p.dk3_slots = a->workspace ? (float*)a->workspace + slab_floats : nullptr;
+  if (!p.dk3_slots && hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
     return tdvc_fail(TDVC_ELAUNCH, "film_cond0_bwd: memset failed");
   TDVC_BIG_LDS_ONCE(film_cond0_bwd_kernel); TDVC_TRACE(film_cond0_bwd_kernel);
   const size_t lds = (size_t)(CB_ROWS * CB_S + 8 * CB_S + CB_ROWS * CB_WS + 4 * CB_ROWS * 3) * sizeof(float);
   hipLaunchKernelGGL(film_cond0_bwd_kernel, dim3(nblocks), dim3(256), lds, st, p);
   TDVC_CHECK_LAUNCH();
+  if (p.dk3_slots && launch_dk3_fold(p.dk3_slots, a->dk3, a->B, a->n_cond, p.ntile, p.tpb, st) != hipSuccess)
+    return tdvc_fail(TDVC_ELAUNCH, "film_cond0_bwd: dk3 fold launch failed");
   if (a->dw0) {
     const hipError_t e = launch_slab_reduce(p.slab, nblocks, sstride, sstride, a->dw0 + (long)(a->n_cond - a->n_var) * 3, 24,
                                             (long)a->n_cond * 3, st, -1, nullptr);

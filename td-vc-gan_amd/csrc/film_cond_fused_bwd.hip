@@ -17,8 +17,10 @@
 //       reduces over the chunk's 60 steps (20 accumulator registers per wave, nothing to sum across waves);
 //   (a) P[i][(ce, j)] = sum_c d_cv0[c][i] W0x[c][ce][j] over all 64 columns (rows i = 16w + ln), then the three shifted taps
 //       are summed through a small LDS image: dexc[u][ce] = sum_j P[u + 1 - j][(ce, j)].
-// dW partials stay in registers across the block's chunks (one slab per block, folded by slab_reduce); dk3 partials are
-// flushed with atomics when the block moves to another sample.
+// dW partials stay in registers across the block's chunks (one slab per block, folded by slab_reduce); dk3 partials go to
+// a slot per (block, sample) when the block moves to another sample, summed in block order by dk3_fold_kernel
+// (film_cond_bwd.hip): no atomics, the same bits every run. Without a workspace (no dW wanted) the partials go into the
+// zeroed dk3 with atomics instead.
 #include "conv_common.h"
 #include "api_util.h"
 #include <type_traits>
@@ -27,6 +29,7 @@ PROF_DEFINE(tdvc_debug_condbwd_prof)
 
 namespace tdvc {
 
+hipError_t launch_dk3_fold(const float* slots, float* dk3, int B, int nc, int ntile, int tpb, hipStream_t st);
 hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
                               hipStream_t st, long n_w, float* dbias);
 
@@ -41,7 +44,8 @@ struct CondBwdP {
   const float* exc; long exc_bs;
   const float* w; int w_rs;              // excitation window of cond_var.0's weight: [c][ce][j] at w[c * w_rs + ce * 3 + j]
   float* dexc; long dexc_bs;             // may be null
-  float* dk3;                            // [B][nc][3], zeroed before the launch
+  float* dk3;                            // [B][nc][3]: written by dk3_fold_kernel, or zeroed and accumulated with atomics
+  float* dk3_slots;                      // [nblocks + B][nc][3]: per (block, sample) partials; null = atomics
   float* slab; long slab_stride;         // may be null (no weight gradient wanted)
   int B, T, nc, C2, ntile, tpb, nchunks;
   float slope;
@@ -359,7 +363,10 @@ __global__ __launch_bounds__(256, 2) void film_cond_bwd_kernel(const CondBwdP p)
           const int c = (u - FC_CT) * 16 + ln;
 #pragma unroll
           for (int e = 0; e < 3; ++e) {
-            if (c < p.nc) atomicAdd(p.dk3 + ((long)b * p.nc + c) * 3 + e, acc2[k][e]);
+            if (c < p.nc) {
+              if (p.dk3_slots) p.dk3_slots[(((long)blockIdx.x + b) * p.nc + c) * 3 + e] = acc2[k][e];
+              else atomicAdd(p.dk3 + ((long)b * p.nc + c) * 3 + e, acc2[k][e]);
+            }
             acc2[k][e] = 0.f;
           }
         }
@@ -404,7 +411,7 @@ extern "C" size_t tdvc_film_cond_bwd_workspace(int32_t B, int32_t T, int32_t n_c
   if (B <= 0 || T <= 0 || n_cond <= 0 || n_var != 8) return 0;
   int ntile, tpb, nblocks;
   cond_bwd_plan(B, T, &ntile, &tpb, &nblocks);
-  return (size_t)nblocks * (size_t)n_cond * 24 * sizeof(float);
+  return ((size_t)nblocks * 24 + (size_t)(nblocks + B) * 3) * (size_t)n_cond * sizeof(float);   // dW slabs + dk3 slots
 }
 
 extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream) {
@@ -429,12 +436,15 @@ extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream
   cond_bwd_plan(a->B, a->T, &p.ntile, &p.tpb, &nblocks);
   p.nchunks = a->B * p.ntile;
   const long sstride = (long)a->n_cond * 24;
-  if (a->dw0) {
-    if (!a->workspace || a->workspace_bytes < (size_t)nblocks * sstride * sizeof(float))
-      return tdvc_fail(TDVC_EWORKSPACE, "film_cond_bwd: workspace too small");
-    p.slab = (float*)a->workspace; p.slab_stride = sstride;
-  }
-  if (hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
+  const size_t slab_floats = a->dw0 ? (size_t)nblocks * sstride : 0, slot_floats = (size_t)(nblocks + a->B) * a->n_cond * 3;
+  // workspace: required with dw0 (slabs); without dw0 it is optional -- given, dk3 goes through per-block slots and a
+  // fixed-order fold (the same bits every run), absent, through atomics into the zeroed dk3 (summation order may vary)
+  if (a->dw0 && !a->workspace) return tdvc_fail(TDVC_EWORKSPACE, "film_cond_bwd: workspace needed with dw0");
+  if (a->workspace && a->workspace_bytes < (slab_floats + slot_floats) * sizeof(float))
+    return tdvc_fail(TDVC_EWORKSPACE, "film_cond_bwd: workspace too small");
+  if (a->dw0) { p.slab = (float*)a->workspace; p.slab_stride = sstride; }
+  p.dk3_slots = a->workspace ? (float*)a->workspace + slab_floats : nullptr;
+  if (!p.dk3_slots && hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
     return tdvc_fail(TDVC_ELAUNCH, "film_cond_bwd: memset failed");
   const size_t lds = g_knob[3] ? (size_t)100 * 1024 : (size_t)FC_LDS_FLOATS * sizeof(float);   // knob 3 (diagnostic): one block per CU
   if (p.bits) {
@@ -447,6 +457,8 @@ extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream
     hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, p);
   }
   TDVC_CHECK_LAUNCH();
+  if (p.dk3_slots && launch_dk3_fold(p.dk3_slots, a->dk3, a->B, a->n_cond, p.ntile, p.tpb, st) != hipSuccess)
+    return tdvc_fail(TDVC_ELAUNCH, "film_cond_bwd: dk3 fold launch failed");
   if (a->dw0) {
     const hipError_t e = launch_slab_reduce(p.slab, nblocks, sstride, sstride, a->dw0 + (long)(a->n_cond - a->n_var) * 3, 24,
                                             (long)a->n_cond * 3, st, -1, nullptr);

@@ -436,7 +436,7 @@ class FilmCondFn(Function):
         C2 = ctx.s2.cout
         if FUSED_COND_BWD and ctx.s2.slot.wt and nv == 8 and C2 % 32 == 0 and T % 4 == 0 and nc <= 144 and nc % 4 == 0:
             # one launch: the 136-channel gradient of cond_var.0's output lives in LDS / registers only (film_cond_fused_bwd.hip)
-            nbytes = lib.tdvc_film_cond_bwd_workspace(B, T, nc, nv) if want_w else 0
+            nbytes = lib.tdvc_film_cond_bwd_workspace(B, T, nc, nv)      # dW slabs (when wanted) + dk3 slots
             ws, off = workspace(dgb.device, nbytes) if nbytes else (None, 0)
             bits = ctx.bits
             a = L.FilmCondBwdArgs(B, T, nc, nv, C2, dgb.data_ptr(), _bs(dgb), ctx.s2.slot.wt,
@@ -457,7 +457,7 @@ class FilmCondFn(Function):
                 return dexc, dk3, None, None, None
         dcv = conv_dgrad_raw(ctx.s2, dgb, _xf(), T, L.DG_MASK_LRELU, x_in=cv0, x_bits=ctx.bits)
         # everything that consumes d_cv0 in one pass over it: dexc, the excitation window of cond_var.0's weight-grad, dk3
-        nbytes = lib.tdvc_film_cond0_bwd_workspace(B, T, nc, nv) if want_w else 0
+        nbytes = lib.tdvc_film_cond0_bwd_workspace(B, T, nc, nv)     # dW slabs (when wanted) + dk3 slots
         ws, off = workspace(dgb.device, nbytes) if nbytes else (None, 0)
         a = L.FilmCond0BwdArgs(B, T, nc, nv, dcv.data_ptr(), _bs(dcv), exc.data_ptr(), _bs(exc), sv.w,
                                dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
