@@ -624,7 +624,7 @@ __global__ __launch_bounds__(256) void log_l1_bwd_kernel(const float* a, const f
     const float av = a[i];
     const float d = logf(fmaxf(av, floor_)) - logf(fmaxf(b[i], floor_));
     const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    da[i] = av > floor_ ? sg * u / av : 0.f;     // clamp passes gradient only above the floor
+    da[i] = av >= floor_ ? sg * u / av : 0.f;    // torch.clamp(min=floor) passes the gradient where a >= floor, the floor included
   }
 }
 

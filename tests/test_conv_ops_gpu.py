@@ -222,7 +222,8 @@ def film_block_errors(cfg, dev, B=2):
     return errs
 
 
-@pytest.mark.parametrize('cfg', [(16, 2048, 2), (64, 600, 3), (128, 260, 2), (32, 64, 2)], ids=['C16_T2048', 'C64_T600', 'C128_T260', 'C32_T64'])
+@pytest.mark.parametrize('cfg', [(16, 2048, 2), (64, 600, 3), (128, 260, 2), (32, 64, 2), (32, 260, 120), (32, 96, 1100)],
+                         ids=['C16_T2048', 'C64_T600', 'C128_T260', 'C32_T64', 'C32_T260_B120_split', 'C32_T96_B1100_3samples'])
 @pytest.mark.parametrize('fused_bwd', [True, False], ids=['bwd1launch', 'bwd2launch'])
 @pytest.mark.parametrize('fused_fwd', [False, True], ids=['fwd2launch', 'fwd1launch'])
 def test_film_conditioning_fused(cfg, fused_fwd, fused_bwd, dev):
@@ -230,7 +231,10 @@ def test_film_conditioning_fused(cfg, fused_fwd, fused_bwd, dev):
     the split formulation) against float64 autograd of the dense reference formulation
         gb = cond_var.2(LeakyReLU(cond_var.0(cat([emb.repeat(T), exc])))).
     Ragged cases on purpose: T = 600 / 260 / 64 are not multiples of the fused backward's 60-step chunk or of 32 (fp32 mask
-    source), T = 2048 runs the sign-bit mask with a partial last chunk."""
+    source), T = 2048 runs the sign-bit mask with a partial last chunk. The last two have more than 512 (sample, chunk) pairs
+    in both backward plans (64-step and 60-step chunks), so a block walks several chunks and dk3 is folded from per-(block,
+    sample) slots: at T = 260, B = 120 (5 chunks per sample, 2 per block) a sample's chunks are split across two blocks; at
+    T = 96, B = 1100 (2 chunks per sample, 5 per block) one block covers three samples."""
     ops = _mods()[0]
     old = ops.FUSED_COND_FWD, ops.FUSED_COND_BWD
     ops.FUSED_COND_FWD, ops.FUSED_COND_BWD = fused_fwd, fused_bwd
