@@ -1,40 +1,21 @@
 // C-ABI entry points for the convolution family: maps a (tdvc_conv_desc, args) pair onto the
 // reduced stride-1 problem of conv_common.h and picks the MFMA or the scalar kernel.
 #include "../../include/tdvc.h"
-#include "conv_common.h"
+#include "launch.h"
 #include "conv_lean.h"
-#include "conv_wgrad_lean.h"
 #include "conv_small_group.h"
 #include "api_util.h"
-
-namespace tdvc {
-template <int MODE> hipError_t launch_conv_gemm(GemmConvP, int, hipStream_t);
-template <int MODE> hipError_t launch_conv_scalar(GemmConvP, int, hipStream_t);
-template <int MODE> hipError_t launch_conv_wgrad(WgradP, int, int, hipStream_t);
-template <int MODE> hipError_t launch_conv_wgrad_scalar(WgradP, int, long, float*, hipStream_t);
-int wgrad_geometry(WgradP& p, int B, int* bpb_out);
-bool wgrad_mfma_supported(int J);
-hipError_t launch_slab_reduce(const float*, int, long, long, float*, int, long, hipStream_t, long n_w = -1, float* dbias = nullptr);
-hipError_t launch_bias_grad(const Opnd&, int, int, int, float*, hipStream_t);
-hipError_t fold_flush(hipStream_t st);
-void fold_set_defer(int on);
-void fold_reset(hipStream_t st);
-}  // namespace tdvc
-
-namespace tdvc {
-
-
-}  // namespace tdvc
 
 using namespace tdvc;
 
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline bool ok_bs(const void* p, long bs) { return !p || (bs < (1L << 31)); }
 static inline bool vec_ptr(const void* p, long bs) { return !p || (al16(p) && (bs & 3) == 0); }
+static inline float scale_or_1(float s) { return s == 0.f ? 1.f : s; }   // ABI: a scale of 0 means unset
 
 // Prologue kind of the lean kernel for an operand transform; -1 = not supported there.
 static int lean_xfk(const tdvc_xform& x, float* slope, float* scale, const float** aux, long* aux_bs) {
-  *scale = x.scale == 0.f ? 1.f : x.scale; *aux = x.aux; *aux_bs = x.aux_bs; *slope = x.slope;
+  *scale = scale_or_1(x.scale); *aux = x.aux; *aux_bs = x.aux_bs; *slope = x.slope;
   switch (x.kind) {
     case TDVC_XF_NONE: *slope = 1.f; *aux = nullptr; return LXF_ACT;
     case TDVC_XF_LRELU: *aux = nullptr; return (x.slope >= 0.f && x.slope <= 1.f) ? LXF_ACT : -1;
@@ -53,7 +34,7 @@ namespace tdvc { int g_force_generic = 0; }   // test-only switch, like the tdvc
 extern "C" void tdvc_set_force_generic(int on) { g_force_generic = on; }
 
 static Xf to_xf(const tdvc_xform& x) {
-  Xf r; r.kind = x.kind; r.slope = x.slope; r.scale = x.scale == 0.f ? 1.f : x.scale;  // 0 = unset
+  Xf r; r.kind = x.kind; r.slope = x.slope; r.scale = scale_or_1(x.scale);
   r.aux = x.aux; r.aux_bs = x.aux_bs; return r;
 }
 
@@ -122,8 +103,8 @@ extern "C" int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* 
     SmallGroupP q = {};
     small_group_base(d, q);
     q.x = a->x; q.x_bs = a->x_bs; q.w = a->w; q.bias = a->bias; q.y = a->y; q.y_bs = a->y_bs;
-    q.act_in = a->x_xf.kind == TDVC_XF_LRELU; q.slope_in = a->x_xf.slope; q.in_scale = a->x_xf.scale == 0.f ? 1.f : a->x_xf.scale;
-    q.post = a->post_act; q.post_slope = a->post_slope; q.out_scale = a->out_scale == 0.f ? 1.f : a->out_scale;
+    q.act_in = a->x_xf.kind == TDVC_XF_LRELU; q.slope_in = a->x_xf.slope; q.in_scale = scale_or_1(a->x_xf.scale);
+    q.post = a->post_act; q.post_slope = a->post_slope; q.out_scale = scale_or_1(a->out_scale);
     const hipError_t e = launch_small_group_fwd(q, (hipStream_t)stream);
     if (e == hipSuccess) return TDVC_OK;
     if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
@@ -139,7 +120,7 @@ extern "C" int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* 
       q.x = a->x; q.w = w; q.y = a->y; q.bias = a->bias; q.bias3 = a->bias3; q.res = a->res; q.add = a->add; q.aux = aux;
       q.x_bs = (int)a->x_bs; q.y_bs = (int)a->y_bs; q.res_bs = (int)a->res_bs; q.add_bs = (int)a->add_bs; q.aux_bs = (int)aux_bs;
       q.T = d->Tin; q.Cin = d->Cin; q.Cout = d->Cout; q.Cw = cw; q.K = d->K; q.d = d->dilation; q.pad = d->pad; q.reflect = d->reflect;
-      q.post = a->post_act; q.slope = slope; q.in_scale = scale; q.out_scale = a->out_scale == 0.f ? 1.f : a->out_scale;
+      q.post = a->post_act; q.slope = slope; q.in_scale = scale; q.out_scale = scale_or_1(a->out_scale);
       q.add_scale = 1.f; q.m_slope = a->post_slope;
       q.sbits = a->sign_bits; q.sb_bs = (int)a->sign_bits_bs;
       q.vec = ((d->Tin & 3) == 0 && vec_ptr(a->x, a->x_bs) && vec_ptr(a->y, a->y_bs) && vec_ptr(a->res, a->res_bs) &&
@@ -157,7 +138,7 @@ generic_fwd:
   p.w = a->w; p.K = d->K; p.s = d->stride; p.pad = d->pad; p.groups = d->groups;
   p.y = a->y; p.y_bs = a->y_bs; p.Ty = d->Tout; p.Cy_g = Cout_g;
   p.epi = EPI_FWD; p.bias = a->bias; p.bias3 = a->bias3; p.res = a->res; p.res_bs = a->res_bs;
-  p.post = a->post_act; p.post_slope = a->post_slope; p.out_scale = a->out_scale == 0.f ? 1.f : a->out_scale;
+  p.post = a->post_act; p.post_slope = a->post_slope; p.out_scale = scale_or_1(a->out_scale);
   p.add = a->add; p.add_bs = a->add_bs; p.add_scale = 1.f;
   p.w_sg = (long)Cout_g * Cin_g * d->K;
   if (d->kind == TDVC_CONV) {
@@ -183,7 +164,7 @@ extern "C" int tdvc_conv_dgrad(const tdvc_conv_desc* d, const tdvc_conv_dgrad_ar
     SmallGroupP q = {};
     small_group_base(d, q);
     q.dy = a->dy; q.dy_bs = a->dy_bs; q.w = a->w; q.y = a->dx; q.y_bs = a->dx_bs;
-    q.dy_scale = a->dy_xf.scale == 0.f ? 1.f : a->dy_xf.scale;
+    q.dy_scale = scale_or_1(a->dy_xf.scale);
     if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { q.mask = a->dy_xf.aux; q.mask_bs = a->dy_xf.aux_bs; q.m_slope = a->dy_xf.slope; }
     const hipError_t e = launch_small_group_dgrad(q, (hipStream_t)stream);
     if (e == hipSuccess) return TDVC_OK;
@@ -288,42 +269,70 @@ static bool wgrad_use_mfma(const WgradP& p) {
 static bool wgrad_lean_ok(const tdvc_conv_desc* d) {
   const bool wide = d->Cout >= 32 && d->Cin >= 32;     // register-tile kernel: walks (sample, tile) chunks, any length
   return !g_force_generic && d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->Tin == d->Tout &&
-         (d->Tout > 128 || wide) && wgrad_lean_supported(d->K, d->dilation) && (d->K != 15 || d->Cout <= 16 || d->Cin <= 16);
+         (d->Tout > 128 || wide) && wgrad_lean_supported(d->Cout, d->Cin, d->K, d->dilation);
 }
 
-namespace tdvc {
-int wgrad_lean_nslab(int R, int Cin, int N, int K, int B);
-bool wgrad_x6_ok(int R, int Cin, int T, int K, int dil, int pad, int reflect);
-void wgrad_x6_plan(int R, int T, int B, int* ntiles, int* tpb, int* ngroups);
-hipError_t launch_conv_wgrad_x6(const WgLeanP& q, int B, hipStream_t st);
-}
 // split-bf16 weight-grad kernel (conv_wgrad_x6.hip): the layer geometry it takes
 static bool wgrad_x6_desc_ok(const tdvc_conv_desc* d) {
-  return !g_force_generic && d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->Tin == d->Tout && d->w_cin == 0 &&
-         wgrad_x6_ok(d->Cout, d->Cin, d->Tout, d->K, d->dilation, d->pad, d->reflect);
+  return wgrad_lean_ok(d) && d->w_cin == 0 && wgrad_x6_ok(d->Cout, d->Cin, d->Tout, d->K, d->dilation, d->pad, d->reflect);
+}
+
+// Which weight-grad kernel a call takes and what workspace that takes: written once, read by the query and the launch.
+enum { WG_SMALL_GROUP, WG_X6, WG_LEAN, WG_MFMA, WG_SCALAR };   // in the order they are tried
+struct WgPlan {
+  int route;
+  int nslab; long sstride;   // slabs left for the fold here and their stride in floats
+  bool bias;                 // the slabs carry per-slab bias partials behind the weights
+  int bpb;                   // WG_MFMA: samples per block (wgrad_geometry, which also fills p's tile geometry)
+  size_t bytes;              // workspace the route needs
+};
+
+// First route from `from` on that the descriptor and the call's operands can take; a == null (the workspace query, which
+// has no operands to narrow the choice) takes the operand conditions as met.
+static WgPlan wgrad_plan(const tdvc_conv_desc* d, const tdvc_conv_wgrad_args* a, WgradP& p, int from) {
+  const long wsize = (long)d->groups * p.w_sg;
+  WgPlan pl = {};
+  auto slabs = [&](int route, int nslab, bool bias) {
+    pl.route = route; pl.nslab = nslab; pl.bias = bias; pl.sstride = wsize + (bias ? d->Cout : 0);
+    pl.bytes = (size_t)nslab * (size_t)pl.sstride * sizeof(float);
+    return pl;
+  };
+  if (from <= WG_SMALL_GROUP && small_group_ok(d) &&
+      (!a || (a->x_xf.kind <= TDVC_XF_LRELU && (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))))) {
+    pl.route = WG_SMALL_GROUP; pl.bias = true; pl.bytes = small_group_wgrad_workspace(d->B, d->groups, d->K);
+    return pl;                 // nslab 0: the launcher splits the workspace and folds its slabs, bias partials included, itself
+  }
+  // 3-tap conv with 65..144 input channels (FiLM cond_var.2): the split-bf16 x6 kernel, dy and x read once per 32-row block
+  if (from <= WG_X6 && wgrad_x6_desc_ok(d) &&
+      (!a || (a->x_xf.kind <= TDVC_XF_LRELU && a->dy_xf.kind == TDVC_XF_NONE && scale_or_1(a->x_xf.scale) == 1.f && scale_or_1(a->dy_xf.scale) == 1.f &&
+              (a->x_xf.kind == TDVC_XF_NONE || (a->x_xf.slope > 0.f && a->x_xf.slope <= 1.f)) &&
+              al16(a->x) && al16(a->dy) && (a->x_bs & 3) == 0 && (a->dy_bs & 3) == 0))) {
+    int nt, tpb, nslab;
+    wgrad_x6_plan(d->Cout, d->Tout, d->B, &nt, &tpb, &nslab);
+    return slabs(WG_X6, nslab, true);
+  }
+  if (from <= WG_LEAN && wgrad_lean_ok(d)) return slabs(WG_LEAN, wgrad_lean_nslab(d->Cout, d->Cin, d->Tout, d->K, d->B), true);
+  if (from <= WG_MFMA && wgrad_use_mfma(p)) {
+    const int nslab = wgrad_geometry(p, d->B, &pl.bpb);
+    return slabs(WG_MFMA, nslab, false);
+  }
+  pl.route = WG_SCALAR;      // accumulates into dw directly
+  return pl;
 }
 
 extern "C" size_t tdvc_conv_wgrad_workspace(const tdvc_conv_desc* d) {
   if (check_desc(d)) return 0;
-  size_t small = small_group_ok(d) ? small_group_wgrad_workspace(d->B, d->groups, d->K) : 0;
-  if (wgrad_lean_ok(d)) {
-    size_t lean = (size_t)wgrad_lean_nslab(d->Cout, d->Cin, d->Tout, d->K, d->B) * ((size_t)d->Cout * d->Cin * d->K + d->Cout) * sizeof(float);
-    if (wgrad_x6_desc_ok(d)) {       // which of the two kernels runs depends on the operand transforms: size for either
-      int nt, tpb, ng;
-      wgrad_x6_plan(d->Cout, d->Tout, d->B, &nt, &tpb, &ng);
-      const size_t x6 = (size_t)ng * ((size_t)d->Cout * d->Cin * d->K + d->Cout) * sizeof(float);
-      if (x6 > lean) lean = x6;
-    }
-    return lean;
-  }
   WgradP p = {};
   fill_wgrad(d, nullptr, p);
-  if (!wgrad_use_mfma(p)) return small;
-  int bpb;
-  const int nslab = wgrad_geometry(p, d->B, &bpb);
-  const long wsize = (long)d->groups * p.w_sg;
-  const size_t gen = (size_t)nslab * (size_t)wsize * sizeof(float);
-  return gen > small ? gen : small;
+  // the largest need of the routes a call can take: the operands pick between small-group and generic, and between x6 and
+  // lean. A lean launch that declines is not sized for: its predicate (wgrad_lean_supported) admits no such descriptor.
+  size_t need = 0;
+  for (int from = WG_SMALL_GROUP; from <= WG_LEAN; ) {
+    const WgPlan pl = wgrad_plan(d, nullptr, p, from);
+    if (pl.bytes > need) need = pl.bytes;
+    from = pl.route + 1;
+  }
+  return need;
 }
 
 extern "C" int tdvc_conv_wgrad(const tdvc_conv_desc* d, const tdvc_conv_wgrad_args* a, void* stream) {
@@ -333,86 +342,49 @@ extern "C" int tdvc_conv_wgrad(const tdvc_conv_desc* d, const tdvc_conv_wgrad_ar
   WgradP p = {};
   fill_wgrad(d, a, p);
   const long wsize = (long)d->groups * p.w_sg;
-  hipError_t e = hipSuccess;
-  bool done = false, bias_done = false;
-  if (a->dw && small_group_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU &&
-      (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))) {
-    SmallGroupP q = {};
-    small_group_base(d, q);
-    q.x = a->x; q.x_bs = a->x_bs; q.dy = a->dy; q.dy_bs = a->dy_bs;
-    q.act_in = a->x_xf.kind == TDVC_XF_LRELU; q.slope_in = a->x_xf.slope; q.in_scale = a->x_xf.scale == 0.f ? 1.f : a->x_xf.scale;
-    q.dy_scale = a->dy_xf.scale == 0.f ? 1.f : a->dy_xf.scale;
-    if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { q.mask = a->dy_xf.aux; q.mask_bs = a->dy_xf.aux_bs; q.m_slope = a->dy_xf.slope; }
-    e = launch_small_group_wgrad(q, a->dw, a->dbias, a->workspace, a->workspace_bytes, st);
-    if (e == hipSuccess) return TDVC_OK;
-    if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-    e = hipSuccess;
-  }
-  auto unit_scale = [](float sc) { return sc == 0.f || sc == 1.f; };
-  if (a->dw && wgrad_lean_ok(d) && wgrad_x6_desc_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU && a->dy_xf.kind == TDVC_XF_NONE &&
-      unit_scale(a->x_xf.scale) && unit_scale(a->dy_xf.scale) && (a->x_xf.kind == TDVC_XF_NONE || (a->x_xf.slope > 0.f && a->x_xf.slope <= 1.f)) &&
-      al16(a->x) && al16(a->dy) && (a->x_bs & 3) == 0 && (a->dy_bs & 3) == 0) {
-    // 3-tap conv with 65..144 input channels (FiLM cond_var.2): the split-bf16 x6 kernel, dy and x read once per 32-row block
-    WgLeanP q = {};
-    q.a = p.a; q.x = p.x; q.R = d->Cout; q.Cin = d->Cin; q.N = d->Tout;
-    int nt, tpb, nslab;
-    wgrad_x6_plan(d->Cout, d->Tout, d->B, &nt, &tpb, &nslab);
-    const long sstride = wsize + d->Cout;
-    const size_t need = (size_t)nslab * (size_t)sstride * sizeof(float);
-    if (!a->workspace || a->workspace_bytes < need) return tdvc_fail(TDVC_EWORKSPACE, "conv_wgrad: workspace too small");
-    q.slab = (float*)a->workspace; q.slab_stride = sstride; q.bias_off = a->dbias ? wsize : -1;
-    e = launch_conv_wgrad_x6(q, d->B, st);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-    const int rowlen = d->Cin * d->K;
-    e = launch_slab_reduce(q.slab, nslab, sstride, a->dbias ? sstride : wsize, a->dw, rowlen, rowlen, st, wsize, a->dbias);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-    return TDVC_OK;
-  }
-  if (a->dw && wgrad_lean_ok(d)) {
-    WgLeanP q = {};
-    q.a = p.a; q.x = p.x; q.R = d->Cout; q.Cin = d->Cin; q.N = d->Tout; q.pad = d->pad; q.K = d->K; q.reflect = d->reflect;
-    const int nslab = wgrad_lean_nslab(d->Cout, d->Cin, d->Tout, d->K, d->B);
-    const long sstride = wsize + d->Cout;                       // weights + per-slab bias partials
-    const size_t need = (size_t)nslab * (size_t)sstride * sizeof(float);
-    if (!a->workspace || a->workspace_bytes < need) return tdvc_fail(TDVC_EWORKSPACE, "conv_wgrad: workspace too small");
-    q.slab = (float*)a->workspace; q.slab_stride = sstride;
-    auto okp = [](const Opnd& o) { return al16(o.p) && (o.bs & 3) == 0 && (o.T & 3) == 0 && (!o.xf.aux || (al16(o.xf.aux) && (o.xf.aux_bs & 3) == 0)); };
-    q.vec = (okp(q.a) && okp(q.x)) ? 1 : 0;
-    q.bias_off = a->dbias ? wsize : -1;
-    e = launch_conv_wgrad_lean(q, d->B, d->K, d->dilation, st);
-    if (e == hipSuccess) {
-      const int rowlen = d->Cin * d->K;
-      const long nred = a->dbias ? sstride : wsize;
-      if (d->w_cin > 0) e = launch_slab_reduce(q.slab, nslab, sstride, nred, a->dw + (long)d->w_cin_off * d->K, rowlen, (long)d->w_cin * d->K, st, wsize, a->dbias);
-      else e = launch_slab_reduce(q.slab, nslab, sstride, nred, a->dw, rowlen, rowlen, st, wsize, a->dbias);
-      if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-      done = true; bias_done = true;
-    } else if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-  }
-  if (a->dw && !done) {
-    if (wgrad_use_mfma(p)) {
-      int bpb;
-      const int nslab = wgrad_geometry(p, d->B, &bpb);
-      const size_t need = (size_t)nslab * (size_t)wsize * sizeof(float);
-      if (!a->workspace || a->workspace_bytes < need) return tdvc_fail(TDVC_EWORKSPACE, "conv_wgrad: workspace too small");
+  // dw rows of the module's weight, or of its w_cin window
+  float* dw = (a->dw && d->w_cin > 0) ? a->dw + (long)d->w_cin_off * d->K : a->dw;
+  const long dw_rs = d->w_cin > 0 ? (long)d->w_cin * d->K : p.w_sm;
+  bool bias_done = false;
+  for (int from = WG_SMALL_GROUP; a->dw; ) {
+    const WgPlan pl = wgrad_plan(d, a, p, from);
+    if (pl.route != WG_SMALL_GROUP && pl.bytes && (!a->workspace || a->workspace_bytes < pl.bytes))   // (the small-group launcher declines instead)
+      return tdvc_fail(TDVC_EWORKSPACE, "conv_wgrad: workspace too small");
+    hipError_t e;
+    if (pl.route == WG_SMALL_GROUP) {
+      SmallGroupP q = {};
+      small_group_base(d, q);
+      q.x = a->x; q.x_bs = a->x_bs; q.dy = a->dy; q.dy_bs = a->dy_bs;
+      q.act_in = a->x_xf.kind == TDVC_XF_LRELU; q.slope_in = a->x_xf.slope; q.in_scale = scale_or_1(a->x_xf.scale);
+      q.dy_scale = scale_or_1(a->dy_xf.scale);
+      if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { q.mask = a->dy_xf.aux; q.mask_bs = a->dy_xf.aux_bs; q.m_slope = a->dy_xf.slope; }
+      e = launch_small_group_wgrad(q, a->dw, a->dbias, a->workspace, a->workspace_bytes, st);
+    } else if (pl.route == WG_X6 || pl.route == WG_LEAN) {
+      WgLeanP q = {};
+      q.a = p.a; q.x = p.x; q.R = d->Cout; q.Cin = d->Cin; q.N = d->Tout; q.pad = d->pad; q.K = d->K; q.reflect = d->reflect;
+      q.slab = (float*)a->workspace; q.slab_stride = pl.sstride; q.bias_off = a->dbias ? wsize : -1;
+      auto okp = [](const Opnd& o) { return al16(o.p) && (o.bs & 3) == 0 && (o.T & 3) == 0 && (!o.xf.aux || (al16(o.xf.aux) && (o.xf.aux_bs & 3) == 0)); };
+      q.vec = (okp(q.a) && okp(q.x)) ? 1 : 0;
+      e = pl.route == WG_X6 ? launch_conv_wgrad_x6(q, d->B, st) : launch_conv_wgrad_lean(q, d->B, d->K, d->dilation, st);
+    } else if (pl.route == WG_MFMA) {
       p.slab = (float*)a->workspace; p.slab_stride = wsize;
-      e = p.mode == MODE_DIRECT ? launch_conv_wgrad<MODE_DIRECT>(p, d->B, bpb, st) : launch_conv_wgrad<MODE_DOWN>(p, d->B, bpb, st);
-      if (e == hipSuccess) {
-        const int rowlen = (int)p.w_sm;   // compact slab rows: [Cin_g*K]
-        if (d->w_cin > 0) e = launch_slab_reduce(p.slab, nslab, wsize, wsize, a->dw + (long)d->w_cin_off * d->K, rowlen, (long)d->w_cin * d->K, st);
-        else e = launch_slab_reduce(p.slab, nslab, wsize, wsize, a->dw, rowlen, rowlen, st);
-      }
+      e = p.mode == MODE_DIRECT ? launch_conv_wgrad<MODE_DIRECT>(p, d->B, pl.bpb, st) : launch_conv_wgrad<MODE_DOWN>(p, d->B, pl.bpb, st);
     } else {
-      float* dw_base = a->dw;
-      if (d->w_cin > 0) { p.w_sm = (long)d->w_cin * d->K; dw_base += (long)d->w_cin_off * d->K; }
-      e = p.mode == MODE_DIRECT ? launch_conv_wgrad_scalar<MODE_DIRECT>(p, d->B, wsize, dw_base, st)
-                                : launch_conv_wgrad_scalar<MODE_DOWN>(p, d->B, wsize, dw_base, st);
+      p.w_sm = dw_rs;
+      e = p.mode == MODE_DIRECT ? launch_conv_wgrad_scalar<MODE_DIRECT>(p, d->B, wsize, dw, st)
+                                : launch_conv_wgrad_scalar<MODE_DOWN>(p, d->B, wsize, dw, st);
     }
+    if (e == hipErrorNotSupported && (pl.route == WG_SMALL_GROUP || pl.route == WG_LEAN)) { from = pl.route + 1; continue; }   // declined: the next route
+    if (e == hipSuccess && pl.nslab)     // compact slab rows [Cin_g*K] -> dw rows; bias partials, where carried, -> dbias
+      e = launch_slab_reduce((const float*)a->workspace, pl.nslab, pl.sstride, pl.bias && a->dbias ? pl.sstride : wsize, dw, (int)p.w_sm, dw_rs, st,
+                             wsize, pl.bias ? a->dbias : nullptr);
     if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+    bias_done = pl.bias;
+    break;
   }
   if (a->dbias && !bias_done) {
     Opnd dy; dy.p = a->dy; dy.bs = a->dy_bs; dy.T = d->Tout; dy.Cg = d->Cout / d->groups; dy.xf = to_xf(a->dy_xf);
-    e = launch_bias_grad(dy, d->Tout, d->Cout, d->B, a->dbias, st);
+    const hipError_t e = launch_bias_grad(dy, d->Tout, d->Cout, d->B, a->dbias, st);
     if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
   }
   return TDVC_OK;

@@ -2,7 +2,7 @@
 // gfx950 only: v_mfma_f32_16x16x4_f32 (exact fp32, 64 FLOP/clk/SIMD), 64-wide waves,
 // LDS-staged input tile + weight tile, fused prologue (activation / FiLM) on load and fused
 // epilogue (bias, residual, activation, MRF running mean, activation-grad masks, FiLM grads).
-#include "conv_common.h"
+#include "launch.h"
 
 PROF_DEFINE(tdvc_debug_gemm_prof)
 namespace tdvc {
@@ -1105,7 +1105,7 @@ void fold_reset(hipStream_t st) {
 }
 
 hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
-                              hipStream_t st, long n_w = -1, float* dbias = nullptr) {
+                              hipStream_t st, long n_w, float* dbias) {
   if (n_w < 0) n_w = n;
   int gx = (int)((n + 255) / 256); if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
   int gy = 1;

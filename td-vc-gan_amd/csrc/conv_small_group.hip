@@ -7,14 +7,10 @@
 // us per launch for fwd / input-grad / weight-grad of a 41 MB problem). Here a wave owns one (group, 64 output steps) and
 // a lane one output step: 656 FMAs per lane fed by LDS reads -- the input tile in time-to-depth layout (conflict free),
 // the weights as broadcast float4.
-#include "conv_common.h"
+#include "launch.h"
 #include "conv_small_group.h"
 
 namespace tdvc {
-
-hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
-                              hipStream_t st, long n_w, float* dbias);
-
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -6,8 +6,7 @@
 // J (taps) and D (dilation) are template parameters and the LDS strides are constants, so every fragment
 // address in the MFMA loop is base + immediate: one vector add per step. Fragments of step s+1 are fetched
 // before the MFMAs of step s issue.
-#include "conv_common.h"
-#include "conv_wgrad_lean.h"
+#include "launch.h"
 
 namespace tdvc {
 
@@ -408,8 +407,6 @@ static hipError_t wg_launch(const WgLeanP& p, int B, hipStream_t st) {
   return hipGetLastError();
 }
 
-void wgrad_lean_plan(int R, int Cin, int N, int K, int B, int* ntiles, int* tpb, int* ngroups);
-
 template <int M_REP, int C_REP, int J, int D>
 static hipError_t wt_launch(const WgLeanP& p, int B, hipStream_t st) {
   // aligned long sequences with plain prologues -> float4 prefetch; everything else -> scalar prefetch
@@ -483,14 +480,15 @@ int wgrad_lean_nslab(int R, int Cin, int N, int K, int B) {
   return (R <= 16 || Cin <= 16) ? B * ngroups : ngroups;
 }
 
-bool wgrad_lean_supported(int J, int D) {
-  if (J == 1) return D == 1;
-  if (J == 5 || J == 15) return D == 1;
+bool wgrad_lean_supported(int R, int Cin, int J, int D) {
+  if (J == 15) return D == 1 && (R <= 16 || Cin <= 16);      // wg_launch_jd: no wide 15-tap instance
+  if (J == 1 || J == 5) return D == 1;
   return (J == 3 || J == 7 || J == 11) && (D == 1 || D == 3 || D == 5);
 }
 
 // number of slabs = B * ntiles; slab element layout = module weight layout [R][Cin][K]
 hipError_t launch_conv_wgrad_lean(WgLeanP p, int B, int J, int D, hipStream_t st) {
+  if (!wgrad_lean_supported(p.R, p.Cin, J, D)) return hipErrorNotSupported;
   const int first = -p.pad;
   p.lo = -(((-first) + 3) / 4 * 4);
   p.i0 = first - p.lo;

@@ -16,8 +16,7 @@
 // 54 accumulator tiles spread over the 4 waves (wave = one 16-row half x every second 16-channel tile): dy AND x are read from
 // HBM once per row block (the fp32 kernel's 32 x 32 tiles re-read dy five times). Per chunk: global loads of chunk q + 1 are in
 // flight during the MFMAs of chunk q; split + LDS store; one k-block of 32 steps = 90 MFMAs per wave.
-#include "conv_common.h"
-#include "conv_wgrad_lean.h"
+#include "launch.h"
 #include "api_util.h"
 
 namespace tdvc {

@@ -15,13 +15,10 @@
 // the block moves to another sample (slot = block + sample: unique, since a block's samples start where the previous block's
 // end) and dk3_fold_kernel sums the slots of each sample in block order -- no atomics, the same bits every run. A caller
 // that passes no workspace (no dW wanted) gets the partials added into the zeroed dk3 with atomics instead.
-#include "conv_common.h"
+#include "launch.h"
 #include "api_util.h"
 
 namespace tdvc {
-
-hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
-                              hipStream_t st, long n_w, float* dbias);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -387,12 +384,47 @@ hipError_t launch_dk3_fold(const float* slots, float* dk3, int B, int nc, int nt
   return hipGetLastError();
 }
 
-static void cond0_plan(int B, int T, int* ntile, int* tpb, int* nblocks) {
-  *ntile = (T + CB_NT - 1) / CB_NT;
-  const long nchunks = (long)B * (*ntile);
-  long nb = nchunks < 512 ? nchunks : 512;          // one resident wave of blocks (2 per CU)
-  *tpb = (int)((nchunks + nb - 1) / nb);
-  *nblocks = (int)((nchunks + *tpb - 1) / *tpb);
+FilmCondPlan film_cond_plan(int B, int T, int n_cond, int chunk) {
+  FilmCondPlan pl;
+  pl.ntile = (T + chunk - 1) / chunk;
+  const long nchunks = (long)B * pl.ntile;
+  const long nb = nchunks < 512 ? nchunks : 512;    // one resident wave of blocks (2 per CU)
+  pl.tpb = (int)((nchunks + nb - 1) / nb);
+  pl.nblocks = (int)((nchunks + pl.tpb - 1) / pl.tpb);
+  pl.slab_floats = (size_t)pl.nblocks * 24 * (size_t)n_cond;            // dW slabs
+  pl.slot_floats = (size_t)(pl.nblocks + B) * 3 * (size_t)n_cond;       // dk3 slots
+  return pl;
+}
+
+static int cond_bwd_fail(const char* who, int code, const char* what) {
+  char msg[96];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return tdvc_fail(code, msg);
+}
+
+int FilmCondBwdHost::begin(int chunk) {
+  pl = film_cond_plan(B, T, n_cond, chunk);
+  const size_t slab_floats = dw0 ? pl.slab_floats : 0;
+  // workspace: required with dw0 (slabs); without dw0 it is optional -- given, dk3 goes through per-block slots and a
+  // fixed-order fold (the same bits every run), absent, through atomics into the zeroed dk3 (summation order may vary)
+  if (dw0 && !workspace) return cond_bwd_fail(who, TDVC_EWORKSPACE, "workspace needed with dw0");
+  if (workspace && workspace_bytes < (slab_floats + pl.slot_floats) * sizeof(float))
+    return cond_bwd_fail(who, TDVC_EWORKSPACE, "workspace too small");
+  slab = dw0 ? (float*)workspace : nullptr; slab_stride = dw0 ? (long)n_cond * 24 : 0;
+  dk3_slots = workspace ? (float*)workspace + slab_floats : nullptr;
+  if (!dk3_slots && hipMemsetAsync(dk3, 0, (size_t)B * n_cond * 3 * sizeof(float), st) != hipSuccess)
+    return cond_bwd_fail(who, TDVC_ELAUNCH, "memset failed");
+  return TDVC_OK;
+}
+
+int FilmCondBwdHost::finish() {
+  if (dk3_slots && launch_dk3_fold(dk3_slots, dk3, B, n_cond, pl.ntile, pl.tpb, st) != hipSuccess)
+    return cond_bwd_fail(who, TDVC_ELAUNCH, "dk3 fold launch failed");
+  if (dw0) {
+    const hipError_t e = launch_slab_reduce(slab, pl.nblocks, slab_stride, slab_stride, dw0 + (long)(n_cond - n_var) * 3, 24, (long)n_cond * 3, st);
+    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+  }
+  return TDVC_OK;
 }
 
 }  // namespace tdvc
@@ -401,9 +433,8 @@ using namespace tdvc;
 
 extern "C" size_t tdvc_film_cond0_bwd_workspace(int32_t B, int32_t T, int32_t n_cond, int32_t n_var) {
   if (B <= 0 || T <= 0 || n_cond <= 0 || n_var != 8) return 0;
-  int ntile, tpb, nblocks;
-  cond0_plan(B, T, &ntile, &tpb, &nblocks);
-  return ((size_t)nblocks * 24 + (size_t)(nblocks + B) * 3) * (size_t)n_cond * sizeof(float);   // dW slabs + dk3 slots
+  const FilmCondPlan pl = film_cond_plan(B, T, n_cond, CB_NT);
+  return (pl.slab_floats + pl.slot_floats) * sizeof(float);
 }
 
 extern "C" int tdvc_film_cond0_bwd(const tdvc_film_cond0_bwd_args* a, void* stream) {
@@ -418,32 +449,15 @@ extern "C" int tdvc_film_cond0_bwd(const tdvc_film_cond0_bwd_args* a, void* stre
   p.w_rs = a->n_cond * 3; p.w = a->w0 + (long)(a->n_cond - a->n_var) * 3;
   p.dexc = a->dexc; p.dexc_bs = a->dexc_bs; p.dk3 = a->dk3;
   p.B = a->B; p.T = a->T; p.nc = a->n_cond;
-  int nblocks;
-  cond0_plan(a->B, a->T, &p.ntile, &p.tpb, &nblocks);
-  p.nchunks = a->B * p.ntile;
-  const long sstride = (long)a->n_cond * 24;
-  const size_t slab_floats = a->dw0 ? (size_t)nblocks * sstride : 0, slot_floats = (size_t)(nblocks + a->B) * a->n_cond * 3;
-  // workspace: required with dw0 (slabs); without dw0 it is optional -- given, dk3 goes through per-block slots and a
-  // fixed-order fold (the same bits every run), absent, through atomics into the zeroed dk3 (summation order may vary)
-  if (a->dw0 && !a->workspace) return tdvc_fail(TDVC_EWORKSPACE, "film_cond0_bwd: workspace needed with dw0");
-  if (a->workspace && a->workspace_bytes < (slab_floats + slot_floats) * sizeof(float))
-    return tdvc_fail(TDVC_EWORKSPACE, "film_cond0_bwd: workspace too small");
-  if (a->dw0) { p.slab = (float*)a->workspace; p.slab_stride = sstride; }
-  p.dk3_slots = a->workspace ? (float*)a->workspace + slab_floats : nullptr;
-  if (!p.dk3_slots && hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
-    return tdvc_fail(TDVC_ELAUNCH, "film_cond0_bwd: memset failed");
+  FilmCondBwdHost h = {"film_cond0_bwd", a->B, a->T, a->n_cond, a->n_var, a->dk3, a->dw0, a->workspace, a->workspace_bytes, st};
+  if (int rc = h.begin(CB_NT)) return rc;
+  p.ntile = h.pl.ntile; p.tpb = h.pl.tpb; p.nchunks = a->B * p.ntile;
+  p.slab = h.slab; p.slab_stride = h.slab_stride; p.dk3_slots = h.dk3_slots;
   TDVC_BIG_LDS_ONCE(film_cond0_bwd_kernel); TDVC_TRACE(film_cond0_bwd_kernel);
   const size_t lds = (size_t)(CB_ROWS * CB_S + 8 * CB_S + CB_ROWS * CB_WS + 4 * CB_ROWS * 3) * sizeof(float);
-  hipLaunchKernelGGL(film_cond0_bwd_kernel, dim3(nblocks), dim3(256), lds, st, p);
+  hipLaunchKernelGGL(film_cond0_bwd_kernel, dim3(h.pl.nblocks), dim3(256), lds, st, p);
   TDVC_CHECK_LAUNCH();
-  if (p.dk3_slots && launch_dk3_fold(p.dk3_slots, a->dk3, a->B, a->n_cond, p.ntile, p.tpb, st) != hipSuccess)
-    return tdvc_fail(TDVC_ELAUNCH, "film_cond0_bwd: dk3 fold launch failed");
-  if (a->dw0) {
-    const hipError_t e = launch_slab_reduce(p.slab, nblocks, sstride, sstride, a->dw0 + (long)(a->n_cond - a->n_var) * 3, 24,
-                                            (long)a->n_cond * 3, st, -1, nullptr);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-  }
-  return TDVC_OK;
+  return h.finish();
 }
 
 extern "C" int tdvc_film_k3_fwd(const float* emb, int64_t emb_bs, const float* w0, const float* b0, float* k3, int32_t B, int32_t n_const,

@@ -21,17 +21,13 @@
 // a slot per (block, sample) when the block moves to another sample, summed in block order by dk3_fold_kernel
 // (film_cond_bwd.hip): no atomics, the same bits every run. Without a workspace (no dW wanted) the partials go into the
 // zeroed dk3 with atomics instead.
-#include "conv_common.h"
+#include "launch.h"
 #include "api_util.h"
 #include <type_traits>
 
 PROF_DEFINE(tdvc_debug_condbwd_prof)
 
 namespace tdvc {
-
-hipError_t launch_dk3_fold(const float* slots, float* dk3, int B, int nc, int ntile, int tpb, hipStream_t st);
-hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
-                              hipStream_t st, long n_w, float* dbias);
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -395,23 +391,14 @@ __global__ __launch_bounds__(256, 2) void film_cond_bwd_kernel(const CondBwdP p)
   }
 }
 
-static void cond_bwd_plan(int B, int T, int* ntile, int* tpb, int* nblocks) {
-  *ntile = (T + FC_NT - 1) / FC_NT;
-  const long nchunks = (long)B * (*ntile);
-  long nb = nchunks < 512 ? nchunks : 512;          // one resident wave of blocks (2 per CU)
-  *tpb = (int)((nchunks + nb - 1) / nb);
-  *nblocks = (int)((nchunks + *tpb - 1) / *tpb);
-}
-
 }  // namespace tdvc
 
 using namespace tdvc;
 
 extern "C" size_t tdvc_film_cond_bwd_workspace(int32_t B, int32_t T, int32_t n_cond, int32_t n_var) {
   if (B <= 0 || T <= 0 || n_cond <= 0 || n_var != 8) return 0;
-  int ntile, tpb, nblocks;
-  cond_bwd_plan(B, T, &ntile, &tpb, &nblocks);
-  return ((size_t)nblocks * 24 + (size_t)(nblocks + B) * 3) * (size_t)n_cond * sizeof(float);   // dW slabs + dk3 slots
+  const FilmCondPlan pl = film_cond_plan(B, T, n_cond, FC_NT);
+  return (pl.slab_floats + pl.slot_floats) * sizeof(float);
 }
 
 extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream) {
@@ -432,20 +419,11 @@ extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream
   p.w_rs = a->n_cond * 3; p.w = a->w0 + (long)(a->n_cond - a->n_var) * 3;
   p.dexc = a->dexc; p.dexc_bs = a->dexc_bs; p.dk3 = a->dk3;
   p.B = a->B; p.T = a->T; p.nc = a->n_cond; p.slope = a->slope;
-  int nblocks;
-  cond_bwd_plan(a->B, a->T, &p.ntile, &p.tpb, &nblocks);
-  p.nchunks = a->B * p.ntile;
-  const long sstride = (long)a->n_cond * 24;
-  const size_t slab_floats = a->dw0 ? (size_t)nblocks * sstride : 0, slot_floats = (size_t)(nblocks + a->B) * a->n_cond * 3;
-  // workspace: required with dw0 (slabs); without dw0 it is optional -- given, dk3 goes through per-block slots and a
-  // fixed-order fold (the same bits every run), absent, through atomics into the zeroed dk3 (summation order may vary)
-  if (a->dw0 && !a->workspace) return tdvc_fail(TDVC_EWORKSPACE, "film_cond_bwd: workspace needed with dw0");
-  if (a->workspace && a->workspace_bytes < (slab_floats + slot_floats) * sizeof(float))
-    return tdvc_fail(TDVC_EWORKSPACE, "film_cond_bwd: workspace too small");
-  if (a->dw0) { p.slab = (float*)a->workspace; p.slab_stride = sstride; }
-  p.dk3_slots = a->workspace ? (float*)a->workspace + slab_floats : nullptr;
-  if (!p.dk3_slots && hipMemsetAsync(a->dk3, 0, (size_t)a->B * a->n_cond * 3 * sizeof(float), st) != hipSuccess)
-    return tdvc_fail(TDVC_ELAUNCH, "film_cond_bwd: memset failed");
+  FilmCondBwdHost h = {"film_cond_bwd", a->B, a->T, a->n_cond, a->n_var, a->dk3, a->dw0, a->workspace, a->workspace_bytes, st};
+  if (int rc = h.begin(FC_NT)) return rc;
+  p.ntile = h.pl.ntile; p.tpb = h.pl.tpb; p.nchunks = a->B * p.ntile;
+  p.slab = h.slab; p.slab_stride = h.slab_stride; p.dk3_slots = h.dk3_slots;
+  const int nblocks = h.pl.nblocks;
   const size_t lds = g_knob[3] ? (size_t)100 * 1024 : (size_t)FC_LDS_FLOATS * sizeof(float);   // knob 3 (diagnostic): one block per CU
   if (p.bits) {
     auto k = film_cond_bwd_kernel<true>;
@@ -457,12 +435,5 @@ extern "C" int tdvc_film_cond_bwd(const tdvc_film_cond_bwd_args* a, void* stream
     hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), lds, st, p);
   }
   TDVC_CHECK_LAUNCH();
-  if (p.dk3_slots && launch_dk3_fold(p.dk3_slots, a->dk3, a->B, a->n_cond, p.ntile, p.tpb, st) != hipSuccess)
-    return tdvc_fail(TDVC_ELAUNCH, "film_cond_bwd: dk3 fold launch failed");
-  if (a->dw0) {
-    const hipError_t e = launch_slab_reduce(p.slab, nblocks, sstride, sstride, a->dw0 + (long)(a->n_cond - a->n_var) * 3, 24,
-                                            (long)a->n_cond * 3, st, -1, nullptr);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-  }
-  return TDVC_OK;
+  return h.finish();
 }

@@ -101,6 +101,26 @@ def workspace(device, nbytes):
     return ent[0], off
 
 
+def _ws_region(device, nbytes):
+    """(pointer, nbytes) of a fresh workspace region for one weight-grad call; (None, 0) when it needs none."""
+    if not nbytes:
+        return None, 0
+    ws, off = workspace(device, nbytes)
+    return ws.data_ptr() + off, nbytes
+
+
+def _wants_wgrad(s):
+    """Does a backward pass accumulate this slot's weight gradient: not for frozen layers / disabled arenas."""
+    return s.trainable and (s.arena is None or s.arena.wgrad_enabled)
+
+
+def _wgrad_launched(s, device):
+    if s.arena is not None:
+        s.arena.note_grad(s)
+    else:
+        fold_flush(device)              # stand-alone use (tests, tools): the caller reads dw right away
+
+
 # ------------------------------------------------------------------------------- launch recorder (measurement only)
 # bench.py sets RECORDER = [] around ONE eager iteration: every conv-family entry point then appends a description of its
 # call (layer geometry, operand transforms, epilogue, operand shapes -- no tensors), from which the benchmark rebuilds each
@@ -202,22 +222,17 @@ def conv_dgrad_raw(spec: ConvSpec, dy, dy_xf, tin, epilogue=L.DG_PLAIN, x_in=Non
 def conv_wgrad_raw(spec: ConvSpec, x, x_xf, dy, dy_xf):
     """Accumulates into the layer's dW / dbias arena slices. No-op for frozen layers / disabled arenas."""
     s = spec.slot
-    if not s.trainable or (s.arena is not None and not s.arena.wgrad_enabled):
+    if not _wants_wgrad(s):
         return
     B, _, tin = x.shape
     d = spec.desc(B, tin)
     lib = L.lib()
     if RECORDER is not None:
         RECORDER.append(('wgrad', _spec_key(spec), B, tin, x_xf.kind, dy_xf.kind, bool(s.db)))
-    nbytes = lib.tdvc_conv_wgrad_workspace(C.byref(d))
-    ws, off = workspace(x.device, nbytes) if nbytes else (None, 0)
     a = L.ConvWgradArgs(x.data_ptr(), _bs(x), x_xf, dy.data_ptr(), _bs(dy), dy_xf, s.dw, s.db or None,
-                        ws.data_ptr() + off if ws is not None else None, nbytes if ws is not None else 0)
+                        *_ws_region(x.device, lib.tdvc_conv_wgrad_workspace(C.byref(d))))
     L.check(lib.tdvc_conv_wgrad(C.byref(d), C.byref(a), _stream(x)))
-    if s.arena is not None:
-        s.arena.note_grad(s)
-    else:
-        fold_flush(x.device)            # stand-alone use (tests, tools): the caller reads dw right away
+    _wgrad_launched(s, x.device)
 
 
 PRE_NONE, PRE_LRELU = 0, 1
@@ -276,7 +291,7 @@ def _token(*specs):
         return None
     for sp in specs:
         s = sp.slot
-        if s.trainable and s.arena is not None and s.arena.wgrad_enabled:
+        if s.arena is not None and _wants_wgrad(s):
             return s.arena.token
     return None
 
@@ -356,8 +371,16 @@ FUSED_COND_FWD_X6 = os.environ.get('TDVC_FUSED_COND_FWD_X6', '1') == '1'      # 
 FUSED_COND_FWD_X6_ALWAYS = os.environ.get('TDVC_FUSED_COND_FWD_X6_ALWAYS', '0') == '1'      # tests / tools / A-B: also where the two launches measure faster stand-alone
 
 
+def _sign_bits(B, nc, T, device):
+    """Buffer for the signs of cv0, one bit per element ([B, nc, T // 32] int32), where the input-grad of cond_var.2 reads its LeakyReLU
+    mask from them instead of the fp32 tensor; None elsewhere."""
+    if SIGN_BIT_MASKS and T % 32 == 0 and T >= 512:
+        return torch.empty((B, nc, T // 32), dtype=torch.int32, device=device)
+    return None
+
+
 def _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2):
-    """One launch for the conditioning forward (tdvc_film_cond_fwd_x6): returns gb and leaves cv0 / sign bits on ctx, or None when the
+    """One launch for the conditioning forward (tdvc_film_cond_fwd_x6): returns (gb, cv0, sign bits), or None when the
     shape is outside the kernel's contract (the caller then runs the two launches)."""
     B, nv, T = exc.shape
     nc, C2 = spec2.cin, spec2.cout
@@ -371,7 +394,7 @@ def _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2):
     keep = any(ctx.needs_input_grad)      # inference / no_grad: the intermediate is not stored at all
     cv0 = torch.empty((B, nc, T), dtype=torch.float32, device=exc.device) if keep else None
     gb = torch.empty((B, C2, T), dtype=torch.float32, device=exc.device)
-    bits = torch.empty((B, nc, T // 32), dtype=torch.int32, device=exc.device) if (keep and SIGN_BIT_MASKS and T % 32 == 0 and T >= 512) else None
+    bits = _sign_bits(B, nc, T, exc.device) if keep else None
     a = L.FilmCondArgs(B, T, nc, nv, C2, exc.data_ptr(), _bs(exc), spec_var.slot.w, k3.data_ptr(), spec2.slot.w, spec2.slot.b or None,
                        cv0.data_ptr() if keep else None, _bs(cv0) if keep else 0, gb.data_ptr(), _bs(gb), SLOPE)
     rc = lib.tdvc_film_cond_fwd_x6(C.byref(a), _weight_planes_x6(spec2, exc.device).data_ptr(), bits.data_ptr() if bits is not None else None,
@@ -381,8 +404,7 @@ def _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2):
     L.check(rc)
     if RECORDER is not None:
         RECORDER.append(('film_cond_fwd_x6', B, T, nc, nv, C2, bits is not None))
-    ctx.cv0_tmp, ctx.bits_tmp = cv0, bits
-    return gb
+    return gb, cv0, bits
 
 
 class FilmCondFn(Function):
@@ -403,17 +425,15 @@ class FilmCondFn(Function):
             a = L.FilmCondArgs(B, T, nc, nv, spec2.cout, exc.data_ptr(), _bs(exc), spec_var.slot.w, k3.data_ptr(),
                                spec2.slot.w, spec2.slot.b or None, cv0.data_ptr(), _bs(cv0), gb.data_ptr(), _bs(gb), SLOPE)
             L.check(L.lib().tdvc_film_cond_fwd(C.byref(a), _stream(exc)))
-        elif FUSED_COND_FWD_X6 and X6_FWD and (gb := _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2)) is not None:
-            cv0, bits = ctx.cv0_tmp, ctx.bits_tmp
-            del ctx.cv0_tmp, ctx.bits_tmp
+        elif FUSED_COND_FWD_X6 and X6_FWD and (fused := _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2)) is not None:
+            gb, cv0, bits = fused
         else:
             # two launches: the 8-channel excitation window of cond_var.0 (HBM-bound, writes the 136-channel intermediate
             # once) and cond_var.2 on it with LeakyReLU-on-load. Measured faster than the single fused launch at every
             # decoder stage once the plain kernel runs 3 blocks per CU (tools/tile_sweep.py).
             # the input-grad of cond_var.2 only needs the SIGN of cv0 (LeakyReLU mask): one bit per element, written by the
             # launch that produces cv0, instead of re-reading the 136-channel fp32 tensor (the largest of the step)
-            if SIGN_BIT_MASKS and T % 32 == 0 and T >= 512:
-                bits = torch.empty((B, nc, T // 32), dtype=torch.int32, device=exc.device)
+            bits = _sign_bits(B, nc, T, exc.device)
             cv0 = conv_fwd_raw(spec_var, exc, _xf(), bias3=k3, sign_bits=bits)
             gb = conv_fwd_raw(spec2, cv0, _xf(L.XF_LRELU))
         ctx.sv, ctx.s2 = spec_var, spec2
@@ -430,46 +450,37 @@ class FilmCondFn(Function):
         lib = L.lib()
         sv = ctx.sv.slot
         nv = exc.shape[1]
-        want_w = sv.trainable and (sv.arena is None or sv.arena.wgrad_enabled)
+        want_w = _wants_wgrad(sv)
         dexc = torch.empty_like(exc) if ctx.needs_input_grad[0] else None
         dk3 = torch.empty((B, nc, 3), dtype=torch.float32, device=dgb.device)
         C2 = ctx.s2.cout
+        rec = None
         if FUSED_COND_BWD and ctx.s2.slot.wt and nv == 8 and C2 % 32 == 0 and T % 4 == 0 and nc <= 144 and nc % 4 == 0:
             # one launch: the 136-channel gradient of cond_var.0's output lives in LDS / registers only (film_cond_fused_bwd.hip)
-            nbytes = lib.tdvc_film_cond_bwd_workspace(B, T, nc, nv)      # dW slabs (when wanted) + dk3 slots
-            ws, off = workspace(dgb.device, nbytes) if nbytes else (None, 0)
             bits = ctx.bits
             a = L.FilmCondBwdArgs(B, T, nc, nv, C2, dgb.data_ptr(), _bs(dgb), ctx.s2.slot.wt,
                                   bits.data_ptr() if bits is not None else None, _bs(bits) if bits is not None else 0,
                                   cv0.data_ptr(), _bs(cv0), exc.data_ptr(), _bs(exc), sv.w,
                                   dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
                                   dk3.data_ptr(), sv.dw if want_w else None,
-                                  ws.data_ptr() + off if ws is not None else None, nbytes if ws is not None else 0, SLOPE)
+                                  *_ws_region(dgb.device, lib.tdvc_film_cond_bwd_workspace(B, T, nc, nv)), SLOPE)   # dW slabs (when wanted) + dk3 slots
             rc = lib.tdvc_film_cond_bwd(C.byref(a), _stream(dgb))
             if rc != L.EUNSUPPORTED:
                 L.check(rc)
-                if RECORDER is not None:
-                    RECORDER.append(('film_cond_bwd', B, T, nc, nv, C2, bits is not None, dexc is not None, want_w))
-                if want_w and sv.arena is not None:
-                    sv.arena.note_grad(sv)
-                elif want_w:
-                    fold_flush(dgb.device)
-                return dexc, dk3, None, None, None
-        dcv = conv_dgrad_raw(ctx.s2, dgb, _xf(), T, L.DG_MASK_LRELU, x_in=cv0, x_bits=ctx.bits)
-        # everything that consumes d_cv0 in one pass over it: dexc, the excitation window of cond_var.0's weight-grad, dk3
-        nbytes = lib.tdvc_film_cond0_bwd_workspace(B, T, nc, nv)     # dW slabs (when wanted) + dk3 slots
-        ws, off = workspace(dgb.device, nbytes) if nbytes else (None, 0)
-        a = L.FilmCond0BwdArgs(B, T, nc, nv, dcv.data_ptr(), _bs(dcv), exc.data_ptr(), _bs(exc), sv.w,
-                               dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
-                               dk3.data_ptr(), sv.dw if want_w else None,
-                               ws.data_ptr() + off if ws is not None else None, nbytes if ws is not None else 0)
-        L.check(lib.tdvc_film_cond0_bwd(C.byref(a), _stream(dgb)))
+                rec = ('film_cond_bwd', B, T, nc, nv, C2, bits is not None, dexc is not None, want_w)
+        if rec is None:
+            dcv = conv_dgrad_raw(ctx.s2, dgb, _xf(), T, L.DG_MASK_LRELU, x_in=cv0, x_bits=ctx.bits)
+            # everything that consumes d_cv0 in one pass over it: dexc, the excitation window of cond_var.0's weight-grad, dk3
+            a = L.FilmCond0BwdArgs(B, T, nc, nv, dcv.data_ptr(), _bs(dcv), exc.data_ptr(), _bs(exc), sv.w,
+                                   dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
+                                   dk3.data_ptr(), sv.dw if want_w else None,
+                                   *_ws_region(dgb.device, lib.tdvc_film_cond0_bwd_workspace(B, T, nc, nv)))   # dW slabs (when wanted) + dk3 slots
+            L.check(lib.tdvc_film_cond0_bwd(C.byref(a), _stream(dgb)))
+            rec = ('film_cond0_bwd', B, T, nc, nv, dexc is not None, want_w)
         if RECORDER is not None:
-            RECORDER.append(('film_cond0_bwd', B, T, nc, nv, dexc is not None, want_w))
-        if want_w and sv.arena is not None:
-            sv.arena.note_grad(sv)
-        elif want_w:
-            fold_flush(dgb.device)
+            RECORDER.append(rec)
+        if want_w:
+            _wgrad_launched(sv, dgb.device)
         return dexc, dk3, None, None, None
 
 
@@ -495,7 +506,7 @@ class FilmK3Fn(Function):
         dk3 = dk3.contiguous()
         B, n_const = emb.shape
         s = ctx.spec.slot
-        want_w = s.trainable and (s.arena is None or s.arena.wgrad_enabled)
+        want_w = _wants_wgrad(s)
         demb = torch.empty_like(emb) if ctx.needs_input_grad[0] else None
         L.check(L.lib().tdvc_film_k3_bwd(dk3.data_ptr(), emb.data_ptr(), emb.stride(0), s.w, demb.data_ptr() if demb is not None else None,
                                          s.dw if want_w else None, (s.db or None) if want_w else None, B, n_const, ctx.spec.cout, _stream(dk3)))
@@ -534,7 +545,7 @@ class FilmK3MultiFn(Function):
         B, n_const = emb.shape
         n = len(specs)
         dk = [(g.contiguous() if g is not None else torch.zeros((B, specs[0].cout, 3), dtype=torch.float32, device=emb.device)) for g in dk3s]
-        want = [sp.slot.trainable and (sp.slot.arena is None or sp.slot.arena.wgrad_enabled) for sp in specs]
+        want = [_wants_wgrad(sp.slot) for sp in specs]
         demb = torch.empty_like(emb) if ctx.needs_input_grad[0] else None
         pd = (C.c_void_p * n)(*[t.data_ptr() for t in dk])
         w0 = (C.c_void_p * n)(*[sp.slot.w for sp in specs])
