@@ -26,10 +26,6 @@ static int lean_xfk(const tdvc_xform& x, float* slope, float* scale, const float
   }
 }
 
-static bool lean_shape_ok(const tdvc_conv_desc* d) {
-  return d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->Tin == d->Tout && ((d->Tin & 3) == 0 || d->Tin <= 80);
-}
-
 namespace tdvc { int g_force_generic = 0; }   // test-only switch, like the tdvc_debug_* hooks (misc_kernels.hip)
 extern "C" void tdvc_set_force_generic(int on) { g_force_generic = on; }
 
@@ -65,6 +61,26 @@ static int check_desc(const tdvc_conv_desc* d) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// What a launch result means to an entry point: TDVC_OK, the recorded TDVC_ELAUNCH or, from a route that may decline
+// (hipErrorNotSupported: outside that kernel's contract), TRY_NEXT. TRY_NEXT never leaves this file.
+enum { TRY_NEXT = 1 };
+static int launch_rc(hipError_t e, bool may_decline = false) {
+  if (e == hipSuccess) return TDVC_OK;
+  if (may_decline && e == hipErrorNotSupported) return TRY_NEXT;
+  return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+}
+
+// The reduced stride-1 problem of conv_common.h for a pass that writes T columns of R rows per group, reduced over C channels
+// per group (GemmConvP and WgradP). The weight strides differ per pass and stay with the caller.
+template <class P>
+static void set_reduced(P& p, int mode, int R, int C, int T, const tdvc_conv_desc* d) {
+  const int s = d->stride;
+  p.mode = mode; p.R = R; p.Cred = C; p.N = T; p.J = ceil_div(d->K, s); p.d = 1;
+  if (mode == MODE_DIRECT) p.d = d->dilation;                         // s == 1: J = K
+  else if (mode == MODE_DOWN) p.Cred = C * s;                         // time-to-depth: s phases per channel
+  else { p.R = R * s; p.N = (T - 1 + d->pad) / s + 1; }               // MODE_UP: s output phases per row
+}
+
 // Grouped strided conv with 4 -> 4 channels per group (discriminator layer 4): vector-ALU kernels of conv_small_group.hip
 static bool small_group_ok(const tdvc_conv_desc* d) {
   return !g_force_generic && g_knob[2] == 0 && d->kind == TDVC_CONV && d->groups >= 16 && d->Cin == 4 * d->groups && d->Cout == 4 * d->groups &&
@@ -83,8 +99,7 @@ static bool use_mfma(const GemmConvP& p) {
 
 template <int MODE>
 static int run_gemm(GemmConvP& p, int B, hipStream_t st) {
-  hipError_t e = use_mfma(p) ? launch_conv_gemm<MODE>(p, B, st) : launch_conv_scalar<MODE>(p, B, st);
-  return e == hipSuccess ? TDVC_OK : tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+  return launch_rc(use_mfma(p) ? launch_conv_gemm<MODE>(p, B, st) : launch_conv_scalar<MODE>(p, B, st));
 }
 
 static int dispatch_gemm(GemmConvP& p, int B, hipStream_t st) {
@@ -95,44 +110,65 @@ static int dispatch_gemm(GemmConvP& p, int B, hipStream_t st) {
   }
 }
 
+// Which kernel a forward or an input-grad call takes, in the order they are tried. The launchers of the first two may decline.
+enum { CV_SMALL_GROUP, CV_LEAN, CV_GENERIC };   // CV_GENERIC: the MFMA or the scalar kernel (use_mfma)
+
+static bool lean_shape_ok(const tdvc_conv_desc* d) {
+  return !g_force_generic && d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->Tin == d->Tout && ((d->Tin & 3) == 0 || d->Tin <= 80);
+}
+
+// The lean parameter block of either pass. The caller has put the pass's operands into their roles: q.x, q.w with rows of q.Cw floats,
+// q.y, the optional q.res / add / mx / gb / dgb, and Cin / Cout / pad as the kernel sees them (the input-grad reads dy and wt and writes
+// dx, channel counts swapped, padding flipped). bs: the batch strides of x, y, res, add, mx, gb, dgb. xf brings the aux operand.
+// False: outside the lean kernel's contract (the next route).
+static bool lean_fill(const tdvc_conv_desc* d, const tdvc_xform& xf, const long (&bs)[7], LeanP& q, int* xfk) {
+  long aux_bs;
+  *xfk = lean_xfk(xf, &q.slope, &q.in_scale, &q.aux, &aux_bs);
+  const struct { const void* p; long bs; int* q_bs; } opnds[] = {{q.x, bs[0], &q.x_bs}, {q.y, bs[1], &q.y_bs}, {q.res, bs[2], &q.res_bs}, {q.add, bs[3], &q.add_bs},
+      {q.mx, bs[4], &q.mx_bs}, {q.gb, bs[5], &q.gb_bs}, {q.dgb, bs[6], &q.dgb_bs}, {q.aux, aux_bs, &q.aux_bs}};
+  bool ok = *xfk >= 0 && (q.Cw & 3) == 0 && al16(q.w), vec = (d->Tin & 3) == 0;
+  for (const auto& o : opnds) { ok = ok && ok_bs(o.p, o.bs); vec = vec && vec_ptr(o.p, o.bs); *o.q_bs = (int)o.bs; }
+  q.T = d->Tin; q.K = d->K; q.d = d->dilation; q.vec = vec ? 1 : 0;
+  return ok && (vec || d->Tin <= 80);
+}
+
+// First route from `from` on that the descriptor and the call's operands can take. CV_LEAN comes with q and xfk filled.
+static int fwd_route(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, int from, LeanP& q, int* xfk) {
+  if (from <= CV_SMALL_GROUP && small_group_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU && !a->res && !a->add && !a->bias3) return CV_SMALL_GROUP;
+  if (from <= CV_LEAN && lean_shape_ok(d) && (d->Cin & 3) == 0) {
+    q.x = a->x; q.y = a->y; q.bias = a->bias; q.bias3 = a->bias3; q.res = a->res; q.add = a->add;
+    q.w = a->w + (long)d->w_cin_off * d->K; q.Cw = (d->w_cin > 0 ? d->w_cin : d->Cin) * d->K;
+    q.Cin = d->Cin; q.Cout = d->Cout; q.pad = d->pad; q.reflect = d->reflect;
+    q.post = a->post_act; q.out_scale = scale_or_1(a->out_scale); q.add_scale = 1.f; q.m_slope = a->post_slope;
+    q.sbits = a->sign_bits; q.sb_bs = (int)a->sign_bits_bs;
+    if (lean_fill(d, a->x_xf, {a->x_bs, a->y_bs, a->res_bs, a->add_bs, 0, 0, 0}, q, xfk)) return CV_LEAN;
+  }
+  return CV_GENERIC;
+}
+
 extern "C" int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, void* stream) {
   if (int rc = check_desc(d)) return rc;
   if (!a || !a->x || !a->w || !a->y) return tdvc_fail(TDVC_EINVAL, "conv_fwd: null pointer");
-  const int Cin_g = d->Cin / d->groups, Cout_g = d->Cout / d->groups;
-  if (small_group_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU && !a->res && !a->add && !a->bias3) {
-    SmallGroupP q = {};
-    small_group_base(d, q);
-    q.x = a->x; q.x_bs = a->x_bs; q.w = a->w; q.bias = a->bias; q.y = a->y; q.y_bs = a->y_bs;
-    q.act_in = a->x_xf.kind == TDVC_XF_LRELU; q.slope_in = a->x_xf.slope; q.in_scale = scale_or_1(a->x_xf.scale);
-    q.post = a->post_act; q.post_slope = a->post_slope; q.out_scale = scale_or_1(a->out_scale);
-    const hipError_t e = launch_small_group_fwd(q, (hipStream_t)stream);
-    if (e == hipSuccess) return TDVC_OK;
-    if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+  hipStream_t st = (hipStream_t)stream;
+  LeanP q = {};
+  int xfk = 0, route = CV_SMALL_GROUP;
+  while ((route = fwd_route(d, a, route, q, &xfk)) != CV_GENERIC) {
+    hipError_t e;
+    if (route == CV_SMALL_GROUP) {
+      SmallGroupP g = {};
+      small_group_base(d, g);
+      g.x = a->x; g.x_bs = a->x_bs; g.w = a->w; g.bias = a->bias; g.y = a->y; g.y_bs = a->y_bs;
+      g.act_in = a->x_xf.kind == TDVC_XF_LRELU; g.slope_in = a->x_xf.slope; g.in_scale = scale_or_1(a->x_xf.scale);
+      g.post = a->post_act; g.post_slope = a->post_slope; g.out_scale = scale_or_1(a->out_scale);
+      e = launch_small_group_fwd(g, st);
+    } else e = launch_conv_lean(q, d->B, xfk, EPI_FWD, st);
+    const int rc = launch_rc(e, true);
+    if (rc != TRY_NEXT) return rc;
+    ++route;                           // declined: the next route
   }
-  if (!g_force_generic && lean_shape_ok(d) && (d->Cin & 3) == 0) {
-    LeanP q = {};
-    float slope, scale; const float* aux; long aux_bs;
-    const int xfk = lean_xfk(a->x_xf, &slope, &scale, &aux, &aux_bs);
-    const int cw = (d->w_cin > 0 ? d->w_cin : d->Cin) * d->K;
-    const float* w = a->w + (long)d->w_cin_off * d->K;
-    if (xfk >= 0 && (cw & 3) == 0 && al16(w) && ok_bs(a->x, a->x_bs) && ok_bs(a->y, a->y_bs) && ok_bs(a->res, a->res_bs) &&
-        ok_bs(a->add, a->add_bs) && ok_bs(aux, aux_bs)) {
-      q.x = a->x; q.w = w; q.y = a->y; q.bias = a->bias; q.bias3 = a->bias3; q.res = a->res; q.add = a->add; q.aux = aux;
-      q.x_bs = (int)a->x_bs; q.y_bs = (int)a->y_bs; q.res_bs = (int)a->res_bs; q.add_bs = (int)a->add_bs; q.aux_bs = (int)aux_bs;
-      q.T = d->Tin; q.Cin = d->Cin; q.Cout = d->Cout; q.Cw = cw; q.K = d->K; q.d = d->dilation; q.pad = d->pad; q.reflect = d->reflect;
-      q.post = a->post_act; q.slope = slope; q.in_scale = scale; q.out_scale = scale_or_1(a->out_scale);
-      q.add_scale = 1.f; q.m_slope = a->post_slope;
-      q.sbits = a->sign_bits; q.sb_bs = (int)a->sign_bits_bs;
-      q.vec = ((d->Tin & 3) == 0 && vec_ptr(a->x, a->x_bs) && vec_ptr(a->y, a->y_bs) && vec_ptr(a->res, a->res_bs) &&
-               vec_ptr(a->add, a->add_bs) && vec_ptr(aux, aux_bs)) ? 1 : 0;
-      if (!q.vec && d->Tin > 80) goto generic_fwd;
-      hipError_t e = launch_conv_lean(q, d->B, xfk, EPI_FWD, (hipStream_t)stream);
-      if (e == hipSuccess) return TDVC_OK;
-      if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-    }
-  }
-generic_fwd:
+  // the generic kernels pack no sign bits: only the lean kernel does, inside this contract
   if (a->sign_bits) return tdvc_fail(TDVC_EUNSUPPORTED, "conv_fwd: sign_bits needs a stride-1 conv with Tout % 32 == 0, Tout > 80 and 16-byte aligned operands");
+  const int Cin_g = d->Cin / d->groups, Cout_g = d->Cout / d->groups;
   GemmConvP p = {};
   p.x.p = a->x; p.x.bs = a->x_bs; p.x.T = d->Tin; p.x.Cg = Cin_g; p.x.xf = to_xf(a->x_xf);
   p.w = a->w; p.K = d->K; p.s = d->stride; p.pad = d->pad; p.groups = d->groups;
@@ -144,118 +180,105 @@ generic_fwd:
   if (d->kind == TDVC_CONV) {
     p.w_sm = (long)Cin_g * d->K; p.w_sc = d->K;
     if (d->w_cin > 0) { p.w_sm = (long)d->w_cin * d->K; p.w += (long)d->w_cin_off * d->K; }
-    p.R = Cout_g; p.N = d->Tout;
-    if (d->stride == 1) { p.mode = MODE_DIRECT; p.Cred = Cin_g; p.J = d->K; p.d = d->dilation; p.reflect = d->reflect; }
-    else { p.mode = MODE_DOWN; p.Cred = Cin_g * d->stride; p.J = ceil_div(d->K, d->stride); p.d = 1; }
+    set_reduced(p, d->stride == 1 ? MODE_DIRECT : MODE_DOWN, Cout_g, Cin_g, d->Tout, d);
+    p.reflect = d->reflect;                          // stride 1 only (check_desc)
   } else {
     p.w_sm = d->K; p.w_sc = (long)Cout_g * d->K;
-    p.mode = MODE_UP; p.R = Cout_g * d->stride; p.Cred = Cin_g; p.J = ceil_div(d->K, d->stride); p.d = 1;
-    p.N = (d->Tout - 1 + d->pad) / d->stride + 1;
+    set_reduced(p, MODE_UP, Cout_g, Cin_g, d->Tout, d);
   }
-  return dispatch_gemm(p, d->B, (hipStream_t)stream);
+  return dispatch_gemm(p, d->B, st);
+}
+
+static int dgrad_route(const tdvc_conv_desc* d, const tdvc_conv_dgrad_args* a, int from, LeanP& q, int* xfk) {
+  if (from <= CV_SMALL_GROUP && small_group_ok(d) && a->epilogue == TDVC_DG_PLAIN && !a->add &&
+      (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))) return CV_SMALL_GROUP;
+  if (from <= CV_LEAN && a->wt && lean_shape_ok(d) && (d->Cout & 3) == 0 && (d->K - 1) * d->dilation - d->pad >= 0) {
+    q.x = a->dy; q.y = a->dx; q.add = a->add; q.mx = a->x_in; q.gb = a->gb; q.dgb = a->dgb;
+    q.Cw = d->Cout * d->K; q.w = a->wt + (long)d->w_cin_off * q.Cw;       // wt rows: [ci] -> (co, k) contiguous
+    q.Cin = d->Cout; q.Cout = d->Cin; q.pad = (d->K - 1) * d->dilation - d->pad; q.flip = 1; q.mirror = d->reflect ? d->pad : 0;
+    q.out_scale = 1.f; q.add_scale = a->add_scale; q.m_slope = a->slope;
+    if (a->epilogue == TDVC_DG_MASK_LRELU && a->x_sign_bits) { q.mbits = a->x_sign_bits; q.mb_bs = (int)a->x_sign_bits_bs; }
+    if (lean_fill(d, a->dy_xf, {a->dy_bs, a->dx_bs, 0, a->add_bs, a->x_in_bs, a->gb_bs, a->dgb_bs}, q, xfk)) return CV_LEAN;
+  }
+  return CV_GENERIC;
 }
 
 extern "C" int tdvc_conv_dgrad(const tdvc_conv_desc* d, const tdvc_conv_dgrad_args* a, void* stream) {
   if (int rc = check_desc(d)) return rc;
   if (!a || !a->dy || !a->w || !a->dx) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: null pointer");
-  const int Cin_g = d->Cin / d->groups, Cout_g = d->Cout / d->groups;
-  if (small_group_ok(d) && a->epilogue == TDVC_DG_PLAIN && !a->add &&
-      (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))) {
-    SmallGroupP q = {};
-    small_group_base(d, q);
-    q.dy = a->dy; q.dy_bs = a->dy_bs; q.w = a->w; q.y = a->dx; q.y_bs = a->dx_bs;
-    q.dy_scale = scale_or_1(a->dy_xf.scale);
-    if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { q.mask = a->dy_xf.aux; q.mask_bs = a->dy_xf.aux_bs; q.m_slope = a->dy_xf.slope; }
-    const hipError_t e = launch_small_group_dgrad(q, (hipStream_t)stream);
-    if (e == hipSuccess) return TDVC_OK;
-    if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-  }
-  if (!g_force_generic && a->wt && lean_shape_ok(d) && (d->Cout & 3) == 0 && (d->K - 1) * d->dilation - d->pad >= 0) {
-    LeanP q = {};
-    float slope, scale; const float* aux; long aux_bs;
-    const int xfk = lean_xfk(a->dy_xf, &slope, &scale, &aux, &aux_bs);
-    const int cw = d->Cout * d->K;                                  // wt rows: [ci] -> (co, k) contiguous
-    const float* w = a->wt + (long)d->w_cin_off * cw;
-    const int epi = a->epilogue == TDVC_DG_PLAIN ? EPI_PLAIN : (a->epilogue == TDVC_DG_MASK_LRELU ? EPI_MASK : EPI_FILM);
-    if (xfk >= 0 && (cw & 3) == 0 && al16(w) && ok_bs(a->dy, a->dy_bs) && ok_bs(a->dx, a->dx_bs) && ok_bs(a->add, a->add_bs) &&
-        ok_bs(aux, aux_bs) && ok_bs(a->x_in, a->x_in_bs) && ok_bs(a->gb, a->gb_bs) && ok_bs(a->dgb, a->dgb_bs) &&
-        (epi == EPI_PLAIN || a->x_in || (epi == EPI_MASK && a->x_sign_bits)) && (epi != EPI_FILM || (a->gb && a->dgb))) {
-      q.x = a->dy; q.w = w; q.y = a->dx; q.add = a->add; q.aux = aux; q.mx = a->x_in; q.gb = a->gb; q.dgb = a->dgb;
-      q.x_bs = (int)a->dy_bs; q.y_bs = (int)a->dx_bs; q.add_bs = (int)a->add_bs; q.aux_bs = (int)aux_bs; q.mx_bs = (int)a->x_in_bs;
-      q.gb_bs = (int)a->gb_bs; q.dgb_bs = (int)a->dgb_bs;
-      q.T = d->Tin; q.Cin = d->Cout; q.Cout = d->Cin; q.Cw = cw; q.K = d->K; q.d = d->dilation;
-      q.pad = (d->K - 1) * d->dilation - d->pad; q.flip = 1; q.mirror = d->reflect ? d->pad : 0;
-      q.slope = slope; q.in_scale = scale; q.out_scale = 1.f; q.add_scale = a->add_scale; q.m_slope = a->slope;
-      if (epi == EPI_MASK && a->x_sign_bits) { q.mbits = a->x_sign_bits; q.mb_bs = (int)a->x_sign_bits_bs; }
-      q.vec = ((d->Tin & 3) == 0 && vec_ptr(a->dy, a->dy_bs) && vec_ptr(a->dx, a->dx_bs) && vec_ptr(a->add, a->add_bs) && vec_ptr(aux, aux_bs) &&
-               vec_ptr(a->x_in, a->x_in_bs) && vec_ptr(a->gb, a->gb_bs) && vec_ptr(a->dgb, a->dgb_bs)) ? 1 : 0;
-      if (!q.vec && d->Tin > 80) goto generic_dgrad;
-      hipError_t e = launch_conv_lean(q, d->B, xfk, epi, (hipStream_t)stream);
-      if (e == hipSuccess) return TDVC_OK;
-      if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-      if (q.mbits && a->x_in) {   // shape outside the sign-bit path: the fp32 mask source does the same job
+  // the operands each epilogue reads; x_sign_bits may stand in for x_in on the lean route
+  if (a->epilogue < TDVC_DG_PLAIN || a->epilogue > TDVC_DG_FILM) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: unknown epilogue");
+  const int epi = a->epilogue == TDVC_DG_PLAIN ? EPI_PLAIN : (a->epilogue == TDVC_DG_MASK_LRELU ? EPI_MASK : EPI_FILM);
+  if (epi == EPI_MASK && !a->x_in && !a->x_sign_bits) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: mask epilogue needs x_in");
+  if (epi == EPI_FILM && (!a->x_in || !a->gb || !a->dgb)) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: FiLM epilogue needs x_in, gb, dgb");
+  hipStream_t st = (hipStream_t)stream;
+  LeanP q = {};
+  int xfk = 0, route = CV_SMALL_GROUP;
+  while ((route = dgrad_route(d, a, route, q, &xfk)) != CV_GENERIC) {
+    hipError_t e;
+    if (route == CV_SMALL_GROUP) {
+      SmallGroupP g = {};
+      small_group_base(d, g);
+      g.dy = a->dy; g.dy_bs = a->dy_bs; g.w = a->w; g.y = a->dx; g.y_bs = a->dx_bs;
+      g.dy_scale = scale_or_1(a->dy_xf.scale);
+      if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { g.mask = a->dy_xf.aux; g.mask_bs = a->dy_xf.aux_bs; g.m_slope = a->dy_xf.slope; }
+      e = launch_small_group_dgrad(g, st);
+    } else {
+      e = launch_conv_lean(q, d->B, xfk, epi, st);
+      if (e == hipErrorNotSupported && q.mbits && a->x_in) {   // shape outside the sign-bit path: the fp32 mask source does the same job
         q.mbits = nullptr;
-        e = launch_conv_lean(q, d->B, xfk, epi, (hipStream_t)stream);
-        if (e == hipSuccess) return TDVC_OK;
-        if (e != hipErrorNotSupported) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+        e = launch_conv_lean(q, d->B, xfk, epi, st);
       }
     }
+    const int rc = launch_rc(e, true);
+    if (rc != TRY_NEXT) return rc;
+    ++route;                           // declined: the next route
   }
-generic_dgrad:
-  if (a->epilogue == TDVC_DG_MASK_LRELU && !a->x_in && a->x_sign_bits)
+  // the generic kernels read no sign bits: only the lean kernel does, inside this contract
+  if (epi == EPI_MASK && !a->x_in)
     return tdvc_fail(TDVC_EUNSUPPORTED, "conv_dgrad: x_sign_bits without x_in needs a stride-1 conv with Tin % 32 == 0, Tin > 80 and 16-byte aligned operands");
+  const int Cin_g = d->Cin / d->groups, Cout_g = d->Cout / d->groups;
   GemmConvP p = {};
   p.x.p = a->dy; p.x.bs = a->dy_bs; p.x.T = d->Tout; p.x.Cg = Cout_g; p.x.xf = to_xf(a->dy_xf);
-  p.w = a->w; p.K = d->K; p.s = d->stride; p.groups = d->groups;
-  p.y = a->dx; p.y_bs = a->dx_bs; p.Ty = d->Tin; p.Cy_g = Cin_g; p.N = d->Tin;
+  p.w = a->w; p.K = d->K; p.s = d->stride; p.pad = d->pad; p.groups = d->groups;
+  p.y = a->dx; p.y_bs = a->dx_bs; p.Ty = d->Tin; p.Cy_g = Cin_g;
   p.add = a->add; p.add_bs = a->add_bs; p.add_scale = a->add_scale;
   p.w_sg = (long)Cout_g * Cin_g * d->K;
-  switch (a->epilogue) {
-    case TDVC_DG_PLAIN: p.epi = EPI_PLAIN; break;
-    case TDVC_DG_MASK_LRELU:
-      if (!a->x_in) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: mask epilogue needs x_in");
-      p.epi = EPI_MASK; p.mx = a->x_in; p.mx_bs = a->x_in_bs; p.m_slope = a->slope; break;
-    case TDVC_DG_FILM:
-      if (!a->x_in || !a->gb || !a->dgb) return tdvc_fail(TDVC_EINVAL, "conv_dgrad: FiLM epilogue needs x_in, gb, dgb");
-      p.epi = EPI_FILM; p.mx = a->x_in; p.mx_bs = a->x_in_bs; p.m_slope = a->slope;
-      p.gb = a->gb; p.gb_bs = a->gb_bs; p.dgb = a->dgb; p.dgb_bs = a->dgb_bs; break;
-    default: return tdvc_fail(TDVC_EINVAL, "conv_dgrad: unknown epilogue");
-  }
+  p.epi = epi;
+  if (epi != EPI_PLAIN) { p.mx = a->x_in; p.mx_bs = a->x_in_bs; p.m_slope = a->slope; }
+  if (epi == EPI_FILM) { p.gb = a->gb; p.gb_bs = a->gb_bs; p.dgb = a->dgb; p.dgb_bs = a->dgb_bs; }
   if (d->kind == TDVC_CONV) {
     p.w_sm = d->K; p.w_sc = (long)Cin_g * d->K;      // rows = input channel, reduced channel = output channel
     if (d->w_cin > 0) { p.w_sc = (long)d->w_cin * d->K; p.w += (long)d->w_cin_off * d->K; }
+    set_reduced(p, d->stride == 1 ? MODE_DIRECT : MODE_UP, Cin_g, Cout_g, d->Tin, d);
     if (d->stride == 1) {
-      p.mode = MODE_DIRECT; p.R = Cin_g; p.Cred = Cout_g; p.J = d->K; p.d = d->dilation; p.tap_flip = 1;
-      p.pad = (d->K - 1) * d->dilation - d->pad;
+      p.tap_flip = 1; p.pad = (d->K - 1) * d->dilation - d->pad;
       if (p.pad < 0) return tdvc_fail(TDVC_EUNSUPPORTED, "conv_dgrad: padding larger than the receptive field");
       p.mirror_pad = d->reflect ? d->pad : 0;
-    } else {
-      p.mode = MODE_UP; p.R = Cin_g * d->stride; p.Cred = Cout_g; p.J = ceil_div(d->K, d->stride); p.d = 1; p.pad = d->pad;
-      p.N = (d->Tin - 1 + d->pad) / d->stride + 1;
     }
   } else {
     p.w_sm = (long)Cout_g * d->K; p.w_sc = d->K;      // weight [Cin][Cout_g][K] read as a strided conv over dy
-    p.mode = MODE_DOWN; p.R = Cin_g; p.Cred = Cout_g * d->stride; p.J = ceil_div(d->K, d->stride); p.d = 1; p.pad = d->pad;
+    set_reduced(p, MODE_DOWN, Cin_g, Cout_g, d->Tin, d);
   }
-  return dispatch_gemm(p, d->B, (hipStream_t)stream);
+  return dispatch_gemm(p, d->B, st);
 }
 
 static void fill_wgrad(const tdvc_conv_desc* d, const tdvc_conv_wgrad_args* a, WgradP& p) {
   const int Cin_g = d->Cin / d->groups, Cout_g = d->Cout / d->groups;
   p.groups = d->groups; p.K = d->K; p.s = d->stride; p.pad = d->pad;
-  p.w_sg = (long)Cout_g * Cin_g * d->K;
+  p.w_sg = (long)Cout_g * Cin_g * d->K; p.w_sc = d->K;
   if (d->kind == TDVC_CONV) {
     if (a) { p.a.p = a->dy; p.a.bs = a->dy_bs; p.a.xf = to_xf(a->dy_xf); p.x.p = a->x; p.x.bs = a->x_bs; p.x.xf = to_xf(a->x_xf); }
     p.a.T = d->Tout; p.a.Cg = Cout_g; p.x.T = d->Tin; p.x.Cg = Cin_g;
-    p.R = Cout_g; p.N = d->Tout; p.w_sm = (long)Cin_g * d->K; p.w_sc = d->K;
-    if (d->stride == 1) { p.mode = MODE_DIRECT; p.Cred = Cin_g; p.J = d->K; p.d = d->dilation; p.reflect = d->reflect; }
-    else { p.mode = MODE_DOWN; p.Cred = Cin_g * d->stride; p.J = ceil_div(d->K, d->stride); p.d = 1; }
+    p.w_sm = (long)Cin_g * d->K;
+    set_reduced(p, d->stride == 1 ? MODE_DIRECT : MODE_DOWN, Cout_g, Cin_g, d->Tout, d);
+    p.reflect = d->reflect;                          // stride 1 only (check_desc)
   } else {
     // dW[ci][co][k] = sum_t x[ci][t] * dy[co][t*s - pad + k]: a strided-conv weight-grad with x and dy swapped
     if (a) { p.a.p = a->x; p.a.bs = a->x_bs; p.a.xf = to_xf(a->x_xf); p.x.p = a->dy; p.x.bs = a->dy_bs; p.x.xf = to_xf(a->dy_xf); }
     p.a.T = d->Tin; p.a.Cg = Cin_g; p.x.T = d->Tout; p.x.Cg = Cout_g;
-    p.R = Cin_g; p.N = d->Tin; p.w_sm = (long)Cout_g * d->K; p.w_sc = d->K;
-    p.mode = MODE_DOWN; p.Cred = Cout_g * d->stride; p.J = ceil_div(d->K, d->stride); p.d = 1;
+    p.w_sm = (long)Cout_g * d->K;
+    set_reduced(p, MODE_DOWN, Cin_g, Cout_g, d->Tin, d);
   }
 }
 
@@ -374,18 +397,18 @@ extern "C" int tdvc_conv_wgrad(const tdvc_conv_desc* d, const tdvc_conv_wgrad_ar
       e = p.mode == MODE_DIRECT ? launch_conv_wgrad_scalar<MODE_DIRECT>(p, d->B, wsize, dw, st)
                                 : launch_conv_wgrad_scalar<MODE_DOWN>(p, d->B, wsize, dw, st);
     }
-    if (e == hipErrorNotSupported && (pl.route == WG_SMALL_GROUP || pl.route == WG_LEAN)) { from = pl.route + 1; continue; }   // declined: the next route
-    if (e == hipSuccess && pl.nslab)     // compact slab rows [Cin_g*K] -> dw rows; bias partials, where carried, -> dbias
-      e = launch_slab_reduce((const float*)a->workspace, pl.nslab, pl.sstride, pl.bias && a->dbias ? pl.sstride : wsize, dw, (int)p.w_sm, dw_rs, st,
-                             wsize, pl.bias ? a->dbias : nullptr);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+    int rc = launch_rc(e, pl.route == WG_SMALL_GROUP || pl.route == WG_LEAN);
+    if (rc == TRY_NEXT) { from = pl.route + 1; continue; }   // declined: the next route
+    if (rc == TDVC_OK && pl.nslab)       // compact slab rows [Cin_g*K] -> dw rows; bias partials, where carried, -> dbias
+      rc = launch_rc(launch_slab_reduce((const float*)a->workspace, pl.nslab, pl.sstride, pl.bias && a->dbias ? pl.sstride : wsize, dw, (int)p.w_sm, dw_rs,
+                                        st, wsize, pl.bias ? a->dbias : nullptr));
+    if (rc) return rc;
     bias_done = pl.bias;
     break;
   }
   if (a->dbias && !bias_done) {
     Opnd dy; dy.p = a->dy; dy.bs = a->dy_bs; dy.T = d->Tout; dy.Cg = d->Cout / d->groups; dy.xf = to_xf(a->dy_xf);
-    const hipError_t e = launch_bias_grad(dy, d->Tout, d->Cout, d->B, a->dbias, st);
-    if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
+    return launch_rc(launch_bias_grad(dy, d->Tout, d->Cout, d->B, a->dbias, st));
   }
   return TDVC_OK;
 }
@@ -411,8 +434,4 @@ extern "C" int tdvc_film_cond_fwd(const tdvc_film_cond_args* a, void* stream) {
 // Deferred weight-gradient folds (include/tdvc.h)
 extern "C" void tdvc_fold_defer(int on) { tdvc::fold_set_defer(on); }
 extern "C" void tdvc_fold_reset(void* stream) { tdvc::fold_reset((hipStream_t)stream); }
-extern "C" int tdvc_fold_flush(void* stream) {
-  const hipError_t e = tdvc::fold_flush((hipStream_t)stream);
-  if (e != hipSuccess) return tdvc_fail(TDVC_ELAUNCH, hipGetErrorString(e));
-  return TDVC_OK;
-}
+extern "C" int tdvc_fold_flush(void* stream) { return launch_rc(tdvc::fold_flush((hipStream_t)stream)); }

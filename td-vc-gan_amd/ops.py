@@ -143,6 +143,11 @@ def _bs(t):
     return t.stride(0)
 
 
+def _pb(t):
+    """(pointer, batch stride) of an optional operand: (None, 0) when it is absent."""
+    return (t.data_ptr(), t.stride(0)) if t is not None else (None, 0)
+
+
 def _check_layout(t):
     if t.stride(-1) != 1 or (t.dim() == 3 and t.stride(1) != t.shape[2]):
         raise L.TdvcError('operand must be [B,C,T] with contiguous (C,T) planes')
@@ -174,27 +179,23 @@ def conv_fwd_raw(spec: ConvSpec, x, x_xf, post=L.POST_NONE, res=None, add=None, 
     d = spec.desc(B, tin)
     y = out if out is not None else torch.empty((B, spec.cout, d.Tout), dtype=torch.float32, device=x.device)
     _check_layout(x); _check_layout(y)
+    bias = (b_ptr if b_ptr is not None else spec.slot.b) or None
     if (X6_FWD and spec.k == 3 and spec.kind == L.CONV and spec.stride == 1 and spec.dil == 1 and spec.pad == 1 and spec.groups == 1 and not spec.reflect
             and spec.w_cin == 0 and 64 < spec.cin <= 160 and spec.cout % 32 == 0 and spec.cout >= X6_FWD_MIN_COUT and tin >= 128 and tin % 4 == 0 and post == L.POST_NONE and res is None
             and add is None and bias3 is None and sign_bits is None and w_ptr is None and x_xf.kind in (L.XF_NONE, L.XF_LRELU) and out_scale == 1.0):
-        a = L.ConvFwdArgs(x.data_ptr(), _bs(x), x_xf, spec.slot.w, (b_ptr if b_ptr is not None else spec.slot.b) or None, None, 0, post, SLOPE, 1.0,
+        a = L.ConvFwdArgs(x.data_ptr(), _bs(x), x_xf, spec.slot.w, bias, None, 0, post, SLOPE, 1.0,
                           None, 0, y.data_ptr(), _bs(y), None, None, 0)
         rc = L.lib().tdvc_conv_fwd_x6(C.byref(d), C.byref(a), _weight_planes_x6(spec, x.device).data_ptr(), _stream(x))
         if rc != L.EUNSUPPORTED:
             L.check(rc)
             if RECORDER is not None:
-                RECORDER.append(('fwd_x6', _spec_key(spec), B, tin, x_xf.kind, bool((b_ptr if b_ptr is not None else spec.slot.b))))
+                RECORDER.append(('fwd_x6', _spec_key(spec), B, tin, x_xf.kind, bool(bias)))
             return y
     if RECORDER is not None:
         RECORDER.append(('fwd', _spec_key(spec), B, tin, x_xf.kind, post, res is not None, add is not None,
-                         bool((b_ptr if b_ptr is not None else spec.slot.b)), bias3 is not None, sign_bits is not None))
-    a = L.ConvFwdArgs(x.data_ptr(), _bs(x), x_xf, w_ptr if w_ptr is not None else spec.slot.w,
-                      (b_ptr if b_ptr is not None else spec.slot.b) or None,
-                      res.data_ptr() if res is not None else None, _bs(res) if res is not None else 0,
-                      post, SLOPE, out_scale, add.data_ptr() if add is not None else None,
-                      _bs(add) if add is not None else 0, y.data_ptr(), _bs(y),
-                      bias3.data_ptr() if bias3 is not None else None,
-                      sign_bits.data_ptr() if sign_bits is not None else None, _bs(sign_bits) if sign_bits is not None else 0)
+                         bool(bias), bias3 is not None, sign_bits is not None))
+    a = L.ConvFwdArgs(x.data_ptr(), _bs(x), x_xf, w_ptr if w_ptr is not None else spec.slot.w, bias, *_pb(res),
+                      post, SLOPE, out_scale, *_pb(add), y.data_ptr(), _bs(y), bias3.data_ptr() if bias3 is not None else None, *_pb(sign_bits))
     L.check(L.lib().tdvc_conv_fwd(C.byref(d), C.byref(a), _stream(x)))
     return y
 
@@ -209,12 +210,7 @@ def conv_dgrad_raw(spec: ConvSpec, dy, dy_xf, tin, epilogue=L.DG_PLAIN, x_in=Non
         RECORDER.append(('dgrad', _spec_key(spec), B, tin, dy_xf.kind, epilogue, x_in is not None, x_bits is not None, add is not None,
                          bool(spec.slot.wt)))
     a = L.ConvDgradArgs(dy.data_ptr(), _bs(dy), dy_xf, spec.slot.w, spec.slot.wt or None, epilogue,
-                        x_in.data_ptr() if x_in is not None else None, _bs(x_in) if x_in is not None else 0, SLOPE,
-                        gb.data_ptr() if gb is not None else None, _bs(gb) if gb is not None else 0,
-                        dgb.data_ptr() if dgb is not None else None, _bs(dgb) if dgb is not None else 0,
-                        add.data_ptr() if add is not None else None, _bs(add) if add is not None else 0, add_scale,
-                        dx.data_ptr(), _bs(dx),
-                        x_bits.data_ptr() if x_bits is not None else None, _bs(x_bits) if x_bits is not None else 0)
+                        *_pb(x_in), SLOPE, *_pb(gb), *_pb(dgb), *_pb(add), add_scale, dx.data_ptr(), _bs(dx), *_pb(x_bits))
     L.check(L.lib().tdvc_conv_dgrad(C.byref(d), C.byref(a), _stream(dy)))
     return dx
 
@@ -322,9 +318,7 @@ class FilmBlockFn(Function):
             h, out = torch.empty_like(x), torch.empty_like(x)
             accc = acc.contiguous() if acc is not None else None
             a = L.FilmBlockArgs(B, 16, T, cs.k, cs.dil, x.data_ptr(), _bs(x), cs.slot.w, cs.slot.b or None, h.data_ptr(), _bs(h),
-                                gb.data_ptr() if gb is not None else None, _bs(gb) if gb is not None else 0, ps.slot.w, ps.slot.b or None,
-                                accc.data_ptr() if accc is not None else None, _bs(accc) if accc is not None else 0, scale, SLOPE,
-                                out.data_ptr(), _bs(out))
+                                *_pb(gb), ps.slot.w, ps.slot.b or None, *_pb(accc), scale, SLOPE, out.data_ptr(), _bs(out))
             rc = L.lib().tdvc_film_block_fwd(C.byref(a), _stream(x))
             if rc == L.EUNSUPPORTED:
                 h = out = None
@@ -396,9 +390,8 @@ def _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2):
     gb = torch.empty((B, C2, T), dtype=torch.float32, device=exc.device)
     bits = _sign_bits(B, nc, T, exc.device) if keep else None
     a = L.FilmCondArgs(B, T, nc, nv, C2, exc.data_ptr(), _bs(exc), spec_var.slot.w, k3.data_ptr(), spec2.slot.w, spec2.slot.b or None,
-                       cv0.data_ptr() if keep else None, _bs(cv0) if keep else 0, gb.data_ptr(), _bs(gb), SLOPE)
-    rc = lib.tdvc_film_cond_fwd_x6(C.byref(a), _weight_planes_x6(spec2, exc.device).data_ptr(), bits.data_ptr() if bits is not None else None,
-                                   _bs(bits) if bits is not None else 0, _stream(exc))
+                       *_pb(cv0), gb.data_ptr(), _bs(gb), SLOPE)
+    rc = lib.tdvc_film_cond_fwd_x6(C.byref(a), _weight_planes_x6(spec2, exc.device).data_ptr(), *_pb(bits), _stream(exc))
     if rc == L.EUNSUPPORTED:
         return None
     L.check(rc)
@@ -459,10 +452,8 @@ class FilmCondFn(Function):
             # one launch: the 136-channel gradient of cond_var.0's output lives in LDS / registers only (film_cond_fused_bwd.hip)
             bits = ctx.bits
             a = L.FilmCondBwdArgs(B, T, nc, nv, C2, dgb.data_ptr(), _bs(dgb), ctx.s2.slot.wt,
-                                  bits.data_ptr() if bits is not None else None, _bs(bits) if bits is not None else 0,
-                                  cv0.data_ptr(), _bs(cv0), exc.data_ptr(), _bs(exc), sv.w,
-                                  dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
-                                  dk3.data_ptr(), sv.dw if want_w else None,
+                                  *_pb(bits), cv0.data_ptr(), _bs(cv0), exc.data_ptr(), _bs(exc), sv.w,
+                                  *_pb(dexc), dk3.data_ptr(), sv.dw if want_w else None,
                                   *_ws_region(dgb.device, lib.tdvc_film_cond_bwd_workspace(B, T, nc, nv)), SLOPE)   # dW slabs (when wanted) + dk3 slots
             rc = lib.tdvc_film_cond_bwd(C.byref(a), _stream(dgb))
             if rc != L.EUNSUPPORTED:
@@ -472,8 +463,7 @@ class FilmCondFn(Function):
             dcv = conv_dgrad_raw(ctx.s2, dgb, _xf(), T, L.DG_MASK_LRELU, x_in=cv0, x_bits=ctx.bits)
             # everything that consumes d_cv0 in one pass over it: dexc, the excitation window of cond_var.0's weight-grad, dk3
             a = L.FilmCond0BwdArgs(B, T, nc, nv, dcv.data_ptr(), _bs(dcv), exc.data_ptr(), _bs(exc), sv.w,
-                                   dexc.data_ptr() if dexc is not None else None, _bs(dexc) if dexc is not None else 0,
-                                   dk3.data_ptr(), sv.dw if want_w else None,
+                                   *_pb(dexc), dk3.data_ptr(), sv.dw if want_w else None,
                                    *_ws_region(dgb.device, lib.tdvc_film_cond0_bwd_workspace(B, T, nc, nv)))   # dW slabs (when wanted) + dk3 slots
             L.check(lib.tdvc_film_cond0_bwd(C.byref(a), _stream(dgb)))
             rec = ('film_cond0_bwd', B, T, nc, nv, dexc is not None, want_w)

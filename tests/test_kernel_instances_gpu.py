@@ -482,3 +482,62 @@ def test_sign_bits_refused_outside_contract(dev):
     bits = torch.zeros(2, 16, 16, dtype=torch.int32, device=dev)
     with pytest.raises(L.TdvcError):
         ops.conv_fwd_raw(s, x, ops._xf(), sign_bits=bits)
+
+
+# ------------------------------------------------------------------------------------------------ route fall-through edges
+# tdvc_conv_fwd / tdvc_conv_dgrad try small-group, lean, generic in that order; these pin the edges between lean and generic.
+def test_lean_shaped_conv_off_the_vector_contract_runs_generic(dev):
+    """pw_c64 (64 -> 64, k = 1, T = 333) is lean-shaped, but T % 4 != 0 and T > 80: the generic MFMA kernel takes it."""
+    P = importlib.import_module('td-vc-gan_amd')
+    ops, arena, L = P.ops, P.arena, P._lib
+    case = next(c for c in OPS.CASES if c[0] == 'pw_c64')
+    with traced() as tr:
+        errs = OPS.conv_case_errors(case, dev, 0, B=2)
+    assert max(errs.values()) < TOL, (errs, sorted(tr.names))
+    assert not any(n.startswith('conv_lean_kernel') for n in tr.names), sorted(tr.names)
+    w = torch.randn(64, 64, 1, device=dev)
+    s = ops.ConvSpec(64, 64, 1, 1, 0, 1, 1, False)
+    s.slot = arena.ConvSlot(w.data_ptr(), 0, 0, 0, False, None, 0)
+    with traced() as trf:       # the forward alone
+        ops.conv_fwd_raw(s, torch.randn(2, 64, 333, device=dev), ops._xf(L.XF_LRELU))
+    assert any(n.startswith('conv_gemm_kernel<0,') for n in trf.names), sorted(trf.names)
+    assert not any(n.startswith('conv_lean_kernel') for n in trf.names), sorted(trf.names)
+
+
+def _mask_dgrad_40_24(dev, T):
+    """Input-grad of a 40 -> 24, k = 3, pad 1 conv at B = 2 with the LeakyReLU-mask epilogue: (spec, dy, x_in, sign words of x_in,
+    the weight tensors the spec points into)."""
+    P = importlib.import_module('td-vc-gan_amd')
+    ops, arena = P.ops, P.arena
+    torch.manual_seed(T)
+    w = (torch.randn(24, 40, 3) / 120 ** 0.5).to(dev)
+    wt = w.permute(1, 0, 2).contiguous()
+    s = ops.ConvSpec(40, 24, 3, 1, 1, 1, 1, False)
+    s.slot = arena.ConvSlot(w.data_ptr(), 0, 0, 0, False, None, wt.data_ptr())
+    y = torch.randn(2, 40, T, device=dev)
+    bits = torch.randint(-2 ** 31, 2 ** 31 - 1, (2, 40, (T + 31) // 32), dtype=torch.int32, device=dev)
+    return s, torch.randn(2, 24, T, device=dev), y, bits, (w, wt)
+
+
+def test_sign_bit_dgrad_off_contract_retries_with_fp32_mask(dev):
+    """T = 520 is vector-aligned but T % 32 != 0: the lean launch with the sign words declines and the same launch runs on x_in."""
+    P = importlib.import_module('td-vc-gan_amd')
+    ops, L = P.ops, P._lib
+    s, dy, y, bits, _w = _mask_dgrad_40_24(dev, 520)
+    with traced() as tr:
+        dx_bits = ops.conv_dgrad_raw(s, dy, ops._xf(), 520, L.DG_MASK_LRELU, x_in=y, x_bits=bits)
+    dx_f32 = ops.conv_dgrad_raw(s, dy, ops._xf(), 520, L.DG_MASK_LRELU, x_in=y)
+    assert torch.equal(dx_bits, dx_f32)
+    assert float(dx_bits.abs().max()) > 0
+    assert any(n.startswith('conv_lean_kernel<') and n.endswith(',0,1>') for n in tr.names), sorted(tr.names)
+
+
+def test_sign_bit_dgrad_without_x_in_refused_off_contract(dev):
+    """The same call without the fp32 mask source has nothing to retry with: refused, nothing launched."""
+    P = importlib.import_module('td-vc-gan_amd')
+    ops, L = P.ops, P._lib
+    s, dy, _, bits, _w = _mask_dgrad_40_24(dev, 520)
+    with traced() as tr:
+        with pytest.raises(L.TdvcError):
+            ops.conv_dgrad_raw(s, dy, ops._xf(), 520, L.DG_MASK_LRELU, x_in=None, x_bits=bits)
+    assert not tr.names, sorted(tr.names)
