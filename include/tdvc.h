@@ -354,6 +354,18 @@ int tdvc_cross_entropy_bwd(const float* prob, const int64_t* labels, int B, int 
 int tdvc_f0_to_excitation(const float* f0, const float* noise_v, const float* noise_u, const float* start_phase, float* exc,
                           int B, int n_frames, int step, float sampling_rate, int linear, void* stream);
 
+/* YIN pitch tracker (util/yin.py:24-140, `estimate` and its `soft` variant): x [B][T] (batch stride x_bs) -> f0 [B][n_frames] in Hz,
+ * 0 = non-periodic frame. Frames of L = 2*tau_max samples every `stride` samples over the signal zero-padded by L/2 on the left and
+ * L/2 - 1 on the right (a signal shorter than L is zero-extended to L first); tau_min = int(sr / pitch_max), tau_max =
+ * int(sr / pitch_min), stride = int(frame_stride * sr) are the caller's arithmetic. The difference function is summed directly in
+ * fp32 (the reference takes it from an FFT autocorrelation). soft != 0 selects the softmax-weighted period. cmdf, when not NULL,
+ * receives the cumulative-mean-normalised difference [B][n_frames][tau_max-1-tau_min]. One launch, fixed summation order.
+ * TDVC_EINVAL for T < 1, stride < 1 or tau_max - 1 - tau_min < 2; TDVC_EUNSUPPORTED for tau_max > 1024. */
+/* frames produced for a T-sample signal (host arithmetic only, no GPU needed); <= 0 on bad arguments */
+int tdvc_yin_num_frames(int32_t T, int32_t tau_max, int32_t stride);
+int tdvc_yin_f0(const float* x, int64_t x_bs, int32_t B, int32_t T, int32_t tau_min, int32_t tau_max, int32_t stride,
+                float threshold, int32_t soft, float sample_rate, float* f0, float* cmdf, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X, const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

@@ -155,6 +155,8 @@ SIGNATURES = {
     'tdvc_cross_entropy_fwd': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     'tdvc_cross_entropy_bwd': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     'tdvc_f0_to_excitation': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    'tdvc_yin_num_frames': (_i, [C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_yin_f0': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, _f, _vp, _vp, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

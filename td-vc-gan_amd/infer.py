@@ -1,12 +1,15 @@
 """Forward-only conversion path: what generate_with_target.py:54-184 does around the generator call, with the
 same kernels as the train step — checkpoint interchange (`step{E}-G.pt` / `latest-G.pt` are plain state_dicts with the
-reference's keys), log-F0 mean shift towards the target speaker, excitation on the device, one whole-utterance forward.
+reference's keys), F0 tracking on the device (YIN, pitch.py), log-F0 mean shift towards the target speaker, excitation on the
+device, one whole-utterance forward.
 
-F0 extraction (CREPE, util/crepe.py) and audio I/O stay with the caller: F0 tracks are inputs here.
+`convert_audio` goes from waveform to waveform: `pitch.track_f0` -> F0 scaling -> `convert`. `convert` still takes an F0 track, so a
+caller with a tracker of its own (the reference's CREPE, util/crepe.py) passes that track in. Audio I/O stays with the caller.
 """
 import torch
 
 from . import modules as M
+from .pitch import track_f0
 from .util import f0_to_excitation
 
 SEGMENT_MULT = 320       # product of the decoder ratios (data/dataset.py:41): utterances are padded to a multiple of it
@@ -56,3 +59,12 @@ def convert(G, signal, c_tgt, f0_conv, noise=None, start_phase=None):
     if exc.shape[-1] != T:
         raise ValueError(f'F0 track gives {exc.shape[-1]} excitation samples for a {T}-sample utterance')
     return G(signal, c_tgt, c_var=exc)
+
+
+@torch.no_grad()
+def convert_audio(G, signal, c_tgt, f0_ratio=1.0, noise=None, start_phase=None, **track_kwargs):
+    """Waveform in, waveform out: the F0 track of `signal` [1, 1, T] from `pitch.track_f0` (track_kwargs: hop, sample_rate, pitch_min,
+    pitch_max, threshold), scaled by f0_ratio (the target / source mean-F0 ratio, train.py:636), then `convert`. For the log-F0 mean
+    shift instead, call `track_f0` on both speakers, `shift_f0`, and `convert`."""
+    f0_conv = track_f0(signal, **track_kwargs) * f0_ratio
+    return convert(G, signal, c_tgt, f0_conv, noise=noise, start_phase=start_phase)
