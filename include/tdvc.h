@@ -139,10 +139,15 @@ void tdvc_fold_reset(void* stream);
  * tdvc_debug_force_tile: pin the tile configuration of the lean stride-1 conv kernel (cfg 0..6 = <M_REP,N_REP,WM,WN> of
  *   conv_lean.hip: 0 <1,4,1,4>, 1 <2,4,1,4>, 2 <4,4,1,4>, 3 <1,1,1,4>, 4 <1,4,4,1>, 5 <3,4,1,4>, 6 <1,2,2,2>; -1 = automatic,
  *   grid-aware choice). Lets small test shapes run the instances that only large batches select.
+ * tdvc_debug_force_gemm_tile: pin the tile of the generic MFMA conv kernel (conv_gemm_kernel of conv_mfma.hip: strided, grouped,
+ *   transposed convs and stride-1 convs off the lean contract; forward and input-grad). cfg 0..4 = rows x columns, <M_REP,N_REP,WM,WN>:
+ *   0 16x256 <1,4,1,4>, 1 32x256 <2,4,1,4>, 2 64x256 <4,4,1,4>, 3 16x64 <1,1,1,4>, 4 64x64 <1,4,4,1>; -1 = automatic choice by grid
+ *   size. A pinned tile is taken whatever the row and column count of the problem: the skips of the automatic choice are grid economy, no contract of an instance.
  * tdvc_debug_trace(1) clears and starts, (2) resumes, (0) stops recording the demangled names of the conv-family kernel
  *   instantiations launched; tdvc_debug_trace_dump copies them ('\n'-separated, NUL-terminated) and returns the size needed. */
 void tdvc_set_force_generic(int on);
 void tdvc_debug_force_tile(int cfg);
+void tdvc_debug_force_gemm_tile(int cfg);
 void tdvc_debug_knob(int which, int value); /* tuning knobs for A/B measurements: 0 = XCD-aware block order of the lean conv kernel (1 = on; default 0: measured null on this path); 3 = one block per CU in the fused conditioning backward (diagnostic); 4 = 1: no sample folding of short sequences (T = 16 / 32) in the lean conv kernel; 5 = 1: exact-fp32 MFMA instead of the split-bf16 x6 weight-grad kernel (conv_wgrad_x6.hip); 6 = 1: tdvc_conv_fwd_x6 always answers TDVC_EUNSUPPORTED; 7 = 1: two instead of three resident blocks per CU in the x6 weight-grad's plan */
 void tdvc_debug_lds_cap(int bytes);   /* tuning knob: LDS bytes per block the lean kernel's chunk-size choice may use (0 = built-in) */
 void tdvc_debug_trace(int on);

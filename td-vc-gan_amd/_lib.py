@@ -109,6 +109,7 @@ SIGNATURES = {
     'tdvc_film_cond0_bwd_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_set_force_generic': (None, [_i]),
     'tdvc_debug_force_tile': (None, [_i]),
+    'tdvc_debug_force_gemm_tile': (None, [_i]),
     'tdvc_debug_lds_cap': (None, [_i]),
     'tdvc_debug_knob': (None, [_i, _i]),
     'tdvc_fold_defer': (None, [_i]),

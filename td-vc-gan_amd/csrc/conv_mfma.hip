@@ -903,6 +903,10 @@ hipError_t launch_conv_gemm(GemmConvP p, int B, hipStream_t st) {
     const long blocks = (long)((p.R + c.MT - 1) / c.MT) * ((p.N + c.NT - 1) / c.NT) * p.groups * B;
     if (blocks >= 512) break;
   }
+  if (g_force_gemm_tile >= 0) {   // test-only (tdvc_debug_force_gemm_tile): pin the tile so that small shapes reach every instance.
+    for (const Cand& c : cands)   // The skips above are grid economy, no contract of an instance: a pinned tile is taken as it is.
+      if (c.cfg == g_force_gemm_tile) { MT = c.MT; NT = c.NT; cfg = c.cfg; }
+  }
   const int hi = (MODE == MODE_DIRECT) ? (p.J - 1) * p.d - p.pad + p.mirror_pad : (MODE == MODE_DOWN ? p.J - 1 : 0);
   const int first = (MODE == MODE_DIRECT) ? -p.pad : (MODE == MODE_DOWN ? 0 : -(p.J - 1));   // position read by column 0, tap 0
   int lo = (MODE == MODE_DIRECT) ? -p.pad - p.mirror_pad : first;

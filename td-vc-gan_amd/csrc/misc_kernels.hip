@@ -28,6 +28,7 @@ extern "C" int tdvc_version(void) { return 200; }
 namespace tdvc {
 int g_trace_on = 0;
 int g_force_tile = -1;
+int g_force_gemm_tile = -1;
 int g_lds_cap = 0;
 int g_knob[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 static std::mutex g_trace_mu;
@@ -48,6 +49,7 @@ void trace_kernel(const void* fn) {
 }
 }  // namespace tdvc
 extern "C" void tdvc_debug_force_tile(int cfg) { tdvc::g_force_tile = cfg; }
+extern "C" void tdvc_debug_force_gemm_tile(int cfg) { tdvc::g_force_gemm_tile = cfg; }
 extern "C" void tdvc_debug_lds_cap(int bytes) { tdvc::g_lds_cap = bytes; }
 extern "C" void tdvc_debug_knob(int which, int value) { if (which >= 0 && which < 8) tdvc::g_knob[which] = value; }
 namespace tdvc {
