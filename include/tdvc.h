@@ -371,6 +371,18 @@ int tdvc_yin_num_frames(int32_t T, int32_t tau_max, int32_t stride);
 int tdvc_yin_f0(const float* x, int64_t x_bs, int32_t B, int32_t T, int32_t tau_min, int32_t tau_max, int32_t stride,
                 float threshold, int32_t soft, float sample_rate, float* f0, float* cmdf, void* stream);
 
+/* Backward of tdvc_yin_f0 with soft != 0: upstream gradient gy [B][n_frames] -> dx [B][T] (dense), the gradient of sum(gy * f0)
+ * with respect to x. Frames that are off (no CMDF entry below the threshold), frames with f0 == 0 and frames with gy == 0
+ * contribute exactly zero. The forward's intermediates are recomputed with the forward's own device code. Two launches: one block
+ * per frame writes the frame gradient du [B][n_frames][2*tau_max] to the workspace, a gather sums the frames that cover each
+ * sample in ascending frame order. No atomics (fixed summation order), no allocation, no synchronisation; asynchronous on
+ * `stream` and graph-capturable. Every element of dx is written. Same argument checks and status codes as tdvc_yin_f0, before
+ * any launch; TDVC_EWORKSPACE for a null or too small workspace (tdvc_yin_soft_bwd_workspace bytes, 0 on bad arguments). */
+size_t tdvc_yin_soft_bwd_workspace(int32_t B, int32_t T, int32_t tau_max, int32_t stride);
+int tdvc_yin_soft_bwd(const float* x, int64_t x_bs, int32_t B, int32_t T, int32_t tau_min, int32_t tau_max, int32_t stride,
+                      float threshold, float sample_rate, const float* gy, float* dx, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X, const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

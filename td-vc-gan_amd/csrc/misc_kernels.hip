@@ -484,13 +484,34 @@ __global__ __launch_bounds__(256) void roll_batches_kernel(const float* x, const
 }
 
 // ------------------------------------------------------------------------------ loss reductions
+// Block partials of a loss VALUE reach `out` in an order-independent way, so that a logged loss has the same bits in every run
+// (eager or replayed from a graph): thread 0 of each block adds its partial as a 2^-40 fixed-point integer to a per-kernel device
+// accumulator (integer addition commutes exactly), and the block that arrives last converts the total and adds it to out[0] once.
+// Launches of one kernel are ordered by their stream, so successive launches into the same `out` add in launch order. A partial
+// that is not finite or too large for the fixed-point range goes to `out` as a float atomicAdd, as all partials did before.
+enum { LOSS_MSE = 0, LOSS_L1, LOSS_L1_MULTI, LOSS_LOG_L1, LOSS_CONTRASTIVE, LOSS_CROSS_ENTROPY, LOSS_SITES };
+struct LossAcc { unsigned long long sum; unsigned int arrived; unsigned int pad; };
+__device__ LossAcc g_loss_acc[LOSS_SITES];
+__device__ __forceinline__ void loss_accumulate(float* out, float v, int site) {      // one thread per block calls this
+  LossAcc* a = &g_loss_acc[site];
+  const unsigned int nblocks = gridDim.x * gridDim.y * gridDim.z;
+  if (fabsf(v) < 1048576.f) atomicAdd(&a->sum, (unsigned long long)__double2ll_rn((double)v * 1099511627776.0));
+  else atomicAdd(out, v);                                                            // also NaN: the comparison is false
+  __threadfence();
+  if (atomicAdd(&a->arrived, 1u) == nblocks - 1) {
+    __threadfence();
+    const long long tot = (long long)atomicExch(&a->sum, 0ull);
+    atomicExch(&a->arrived, 0u);
+    atomicAdd(out, (float)((double)tot * (1.0 / 1099511627776.0)));
+  }
+}
 // loss_out[0] += weight * mean((x - target)^2)
 __global__ __launch_bounds__(256) void mse_const_fwd_kernel(const float* x, long n, float target, float w_over_n, float* out) {
   __shared__ float sh[4];
   float s = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) { float d = x[i] - target; s += d * d; }
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) atomicAdd(out, s * w_over_n);
+  if (threadIdx.x == 0) loss_accumulate(out, s * w_over_n, LOSS_MSE);
 }
 __global__ __launch_bounds__(256) void mse_const_bwd_kernel(const float* x, long n, float target, float w2_over_n, const float* up, float* dx) {
   const float u = up ? up[0] : 1.f;
@@ -501,7 +522,7 @@ __global__ __launch_bounds__(256) void l1_fwd_kernel(const float* a, const float
   float s = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += fabsf(a[i] - b[i]);
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) atomicAdd(out, s * w_over_n);
+  if (threadIdx.x == 0) loss_accumulate(out, s * w_over_n, LOSS_L1);
 }
 __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* a, const float* b, long n, float w_over_n, const float* up, float* da, int acc) {
   const float u = (up ? up[0] : 1.f) * w_over_n;
@@ -541,7 +562,7 @@ __global__ __launch_bounds__(256) void l1_multi_fwd_kernel(const L1Batch q, floa
     for (long i = threadIdx.x; i < len; i += 256) s += fabsf(a[i] - b[i]);
   }
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) atomicAdd(out, s * q.w[d]);
+  if (threadIdx.x == 0) loss_accumulate(out, s * q.w[d], LOSS_L1_MULTI);
 }
 // da = sign(a - b) * w * upstream for a pair; b == nullptr: da = 0 (the samples of a batched map that the loss does not read)
 __global__ __launch_bounds__(256) void l1_multi_bwd_kernel(const L1Batch q, const float* up) {
@@ -618,7 +639,7 @@ __global__ __launch_bounds__(256) void log_l1_fwd_kernel(const float* a, const f
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     s += fabsf(logf(fmaxf(a[i], floor_)) - logf(fmaxf(b[i], floor_)));
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) atomicAdd(out, s * w_over_n);
+  if (threadIdx.x == 0) loss_accumulate(out, s * w_over_n, LOSS_LOG_L1);
 }
 __global__ __launch_bounds__(256) void log_l1_bwd_kernel(const float* a, const float* b, long n, float floor_, float w_over_n, const float* up, float* da) {
   const float u = (up ? up[0] : 1.f) * w_over_n;
@@ -711,7 +732,7 @@ __global__ __launch_bounds__(128) void contrastive_kernel(const float* X, const 
     }
     __syncthreads();
   }
-  if (tid == 0) atomicAdd(loss, loss_acc * coef);
+  if (tid == 0) loss_accumulate(loss, loss_acc * coef, LOSS_CONTRASTIVE);
 }
 
 
@@ -771,7 +792,7 @@ __global__ __launch_bounds__(64) void cross_entropy_fwd_kernel(const float* logi
   for (int k = lane; k < K; k += 64) se += expf(z[k] - mx);
   se = wave_sum(se);
   for (int k = lane; k < K; k += 64) prob[(long)b * K + k] = expf(z[k] - mx) / se;
-  if (lane == 0) atomicAdd(loss, (logf(se) + mx - z[labels[b]]) * w_over_b);
+  if (lane == 0) loss_accumulate(loss, (logf(se) + mx - z[labels[b]]) * w_over_b, LOSS_CROSS_ENTROPY);
 }
 __global__ __launch_bounds__(256) void cross_entropy_bwd_kernel(const float* prob, const int64_t* labels, int B, int K, float w_over_b,
                                                                 const float* up, float* dlogits) {

@@ -20,17 +20,9 @@
 #include "../../include/tdvc.h"
 #include "api_util.h"
 #include "conv_common.h"
-#include <limits.h>
+#include "pitch_yin.h"
 
 namespace tdvc {
-
-constexpr int YIN_THREADS = 256;
-constexpr int YIN_WAVES = YIN_THREADS / 64;
-constexpr int YIN_TAU_CAP = 1024;                 // tau_max the ABI accepts: L = 2048 floats = 8 KiB of LDS
-constexpr int YIN_U_FLOATS = 2 * YIN_TAU_CAP + 8; // frame + zeroed tail: the register window reads up to u[L+R+2] (rounded up to 4)
-constexpr int YIN_R = 4;                          // consecutive tau per thread
-static_assert(YIN_R == 4 || YIN_R == 8, "the zeroed tail covers a window of at most 12 values");
-constexpr int YIN_D_FLOATS = YIN_R * YIN_THREADS; // NC slices x (R * NG) rows, NC * NG <= 256
 
 struct YinP {
   const float* x; long x_bs;
@@ -40,172 +32,27 @@ struct YinP {
   float* f0; float* cmdf;
 };
 
-__device__ __forceinline__ int yin_block_min(int v, int* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  int r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r = min(r, red[slot * YIN_WAVES + w]);
-  return r;
-}
-__device__ __forceinline__ float yin_block_minf(float v, float* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  float r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r = fminf(r, red[slot * YIN_WAVES + w]);
-  return r;
-}
-__device__ __forceinline__ float yin_block_sum(float v, float* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // butterfly: the same tree in every lane and every run
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  float r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r += red[slot * YIN_WAVES + w];
-  return r;
-}
-
-// acc[r] += (a_i - w[i + r])^2 for the four j of one step; W = the seven window values u[j+tau0 .. j+tau0+6]
-#define YIN_STEP(acc, a, W)                                        \
-  _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {               \
-    _Pragma("unroll") for (int r_ = 0; r_ < YIN_R; ++r_) {        \
-      float df_ = a[i_] - W[i_ + r_];                              \
-      acc[r_] = fmaf(df_, df_, acc[r_]);                           \
-    }                                                              \
-  }
-
+// The phases live in pitch_yin.h (the soft-YIN backward recomputes them with the same code).
 __global__ __launch_bounds__(YIN_THREADS) void yin_f0_kernel(YinP p) {
   __shared__ __attribute__((aligned(16))) float u[YIN_U_FLOATS];
   __shared__ __attribute__((aligned(16))) float dpart[YIN_D_FLOATS];
-  __shared__ float redf[6 * YIN_WAVES];
+  __shared__ float redf[YIN_RED_SLOTS * YIN_WAVES];
   __shared__ int redi[2 * YIN_WAVES];
 
   const int tid = threadIdx.x;
   const int b = blockIdx.x / p.n_frames, f = blockIdx.x - b * p.n_frames;
   const int L = 2 * p.tau_max;
-  const int Lz = ((L + 3) & ~3) + 8;
 
-  // ---- stage the frame: padded[i] = x[i - L/2] inside [0, T), else 0 (right extension to L and both pads are zeros alike)
-  {
-    const float* xb = p.x + (long)b * p.x_bs;
-    const long s0 = (long)f * p.stride - p.tau_max;
-    for (int j = tid; j < Lz; j += YIN_THREADS) {
-      long s = s0 + j;
-      u[j] = (j < L && s >= 0 && s < p.T) ? xb[s] : 0.f;
-    }
-  }
+  yin_stage_frame(p.x, p.x_bs, p.T, p.tau_max, p.stride, b, f, u);
+  __syncthreads();
+  yin_difference(u, dpart, L, p.NG, p.NC);
   __syncthreads();
 
-  // ---- difference function: thread = (slice c, tau group g)
-  const int g = tid % p.NG, c = tid / p.NG;
-  if (c < p.NC) {
-    constexpr int R = YIN_R;
-    const int tau0 = R * g;
-    const int Lr = L - tau0;                                   // terms of the group's longest row
-    const int ja = ((long)c * Lr / p.NC) & ~3;
-    const int jb = (c + 1 == p.NC) ? ((Lr + 3) & ~3) : (int)(((long)(c + 1) * Lr / p.NC) & ~3);
-    const int jfast = min(jb, (L - (R + 2) - tau0) & ~3);      // steps j < jfast have all 4 * R terms inside their rows
-    const float4* u4 = reinterpret_cast<const float4*>(u);
-    float sum[R], comp[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) sum[r] = comp[r] = 0.f;
-    float W[R + 4];                                            // u[j+tau0 .. j+tau0+R+3]: R held, four read per step
-    int j = ja;
-#pragma unroll
-    for (int q = 0; q < R / 4; ++q) {
-      float4 w0 = u4[((j + tau0) >> 2) + q];
-      W[4 * q] = w0.x; W[4 * q + 1] = w0.y; W[4 * q + 2] = w0.z; W[4 * q + 3] = w0.w;
-    }
-    while (j < jb) {
-      float blk[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) blk[r] = 0.f;
-      if (j + 16 <= jfast) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s, j += 4) {
-          float4 av = u4[j >> 2], wn = u4[((j + tau0) >> 2) + R / 4];
-          float a[4] = {av.x, av.y, av.z, av.w};
-          W[R] = wn.x; W[R + 1] = wn.y; W[R + 2] = wn.z; W[R + 3] = wn.w;
-          YIN_STEP(blk, a, W);
-#pragma unroll
-          for (int q = 0; q < R; ++q) W[q] = W[q + 4];
-        }
-      } else {                                                 // the row ends: at most one short block, terms masked by row length
-        for (int s = 0; s < 4 && j < jb; ++s, j += 4) {
-          float4 av = u4[j >> 2], wn = u4[((j + tau0) >> 2) + R / 4];
-          float a[4] = {av.x, av.y, av.z, av.w};
-          W[R] = wn.x; W[R + 1] = wn.y; W[R + 2] = wn.z; W[R + 3] = wn.w;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              float df = (j + i + tau0 + r < L) ? a[i] - W[i + r] : 0.f;
-              blk[r] = fmaf(df, df, blk[r]);
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < R; ++q) W[q] = W[q + 4];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < R; ++r) {                            // compensated add of the block sum
-        float y = blk[r] - comp[r];
-        float t = sum[r] + y;
-        comp[r] = (t - sum[r]) - y;
-        sum[r] = t;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < R / 4; ++q)
-      reinterpret_cast<float4*>(dpart)[(c * p.NG + g) * (R / 4) + q] = make_float4(sum[4 * q], sum[4 * q + 1], sum[4 * q + 2], sum[4 * q + 3]);
-  }
-  __syncthreads();
-
-  // ---- CMDF: c[k] = d[k+1] * (k+1) / max(sum_{i<=k+1} d[i], 1e-5), k = 0 .. tau_max-2; thread owns k = 4*tid .. 4*tid+3
-  const int n1 = p.tau_max - 1;
-  const int n = n1 - p.tau_min;
-  const int rowlen = YIN_R * p.NG;
+  const int n = p.tau_max - 1 - p.tau_min;
   float* cl = u;                                                // the frame is dead: its LDS holds the CMDF from here on
-  float v[4], pre[4];
   {
-    float run = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int k = 4 * tid + e;
-      float d = 0.f;
-      if (k < n1) {
-        d = dpart[k + 1];
-        for (int s = 1; s < p.NC; ++s) d += dpart[s * rowlen + k + 1];      // slices in order
-      }
-      v[e] = d;
-      run += d;
-      pre[e] = run;
-    }
-    float incl = run;                                           // wave64 inclusive scan of the thread totals
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      float t = __shfl_up(incl, o, 64);
-      if ((tid & 63) >= o) incl += t;
-    }
-    if ((tid & 63) == 63) redf[tid >> 6] = incl;
-    __syncthreads();
-    float base = 0.f;
-    for (int w = 0; w < (tid >> 6); ++w) base += redf[w];
-    base += incl - run;                                         // everything before this thread's four values
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int k = 4 * tid + e;
-      if (k >= p.tau_min && k < n1) {
-        float num = v[e] * (float)(k + 1);                      // product first, then the divide
-        cl[k - p.tau_min] = num / fmaxf(base + pre[e], 1e-5f);
-      }
-    }
+    float d[4], S[4];
+    yin_cmdf(dpart, redf, cl, p.tau_min, p.tau_max, p.NG, p.NC, d, S);
   }
   __syncthreads();
 
@@ -231,21 +78,11 @@ __global__ __launch_bounds__(YIN_THREADS) void yin_f0_kernel(YinP p) {
     tau = (cand == INT_MAX) ? 0.f : (float)cand;
   } else {
     // tau = sum_k softmax(-100 c)[k] * k, times 1 if any c is below the threshold
-    float mn = INFINITY;
-    for (int k = tid; k < n; k += YIN_THREADS) mn = fminf(mn, cl[k]);
-    mn = yin_block_minf(mn, redf, 1);
-    const float xmax = -mn * 100.f;
-    float se = 0.f, sk = 0.f;
-    for (int k = tid; k < n; k += YIN_THREADS) {
-      float e = expf(-cl[k] * 100.f - xmax);
-      se += e;
-      sk = fmaf(e, (float)k, sk);
-    }
-    se = yin_block_sum(se, redf, 2);
-    sk = yin_block_sum(sk, redf, 3);
+    float mn, se, sk;
+    yin_soft_search(cl, n, redf, mn, se, sk);
     tau = (mn < p.threshold) ? sk / se : 0.f;
   }
-  if (tid == 0) p.f0[fr] = tau > 0.f ? p.sample_rate / ((tau + (float)p.tau_min) + 1.f) : 0.f;
+  if (tid == 0) p.f0[fr] = yin_f0_of_tau(tau, p.tau_min, p.sample_rate);
 }
 
 }  // namespace tdvc

@@ -395,6 +395,33 @@ def multiscale_spec_loss(signal, ref, fft_sizes, spectype='both', return_separat
     return total
 
 
+# ------------------------------------------------------------------------------- F0 (soft YIN)
+def f0_yin_loss(signal, f0_tgt, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, threshold=0.1, scale=400.0):
+    """F0 term of the generator loss on the differentiable soft YIN track (pitch.yin_f0(soft=True), csrc/pitch_yin_bwd.hip):
+    signal [B, 1, T], f0_tgt [B, 1, T // hop + 1] in Hz (0 = unvoiced) -> 1-element tensor
+
+        f = soft YIN of signal at stride hop, its first T // hop frames;  t = f0_tgt[..., :-1] (the frame `f0_to_excitation` drops too)
+        v = (t > 0) & (f > 0);  loss = sum(v * ((f - t) / scale)^2) / max(sum(v), 1)
+
+    This is the YIN variant the reference keeps in comments (train.py:438 the soft estimate at frame_stride = 64/16000, :441 the
+    /400 scaling, :466-467 the MSE), restricted to the frames that carry a pitch on both sides. An unmasked MSE would pull a
+    voiced estimate towards 0 Hz wherever the target is unvoiced, and 0 Hz is a value the soft estimate cannot approach
+    continuously (a frame jumps to 0 when it switches off); the other way round an unvoiced estimate has no gradient at all.
+    Everything stays on the device, no host synchronisation; the mask is a constant of the backward pass."""
+    from .pitch import _yin
+    if signal.dim() != 3 or signal.shape[1] != 1:
+        raise ValueError('f0_yin_loss: signal must be [B, 1, T]')
+    f = _yin(signal[:, 0], sample_rate, int(sample_rate / pitch_max), int(sample_rate / pitch_min), int(hop), threshold, True, False)
+    n_t = signal.shape[-1] // int(hop)                     # frames of the track layout [B, 1, T // hop + 1] without its last one
+    if f0_tgt.dim() != 3 or f0_tgt.shape[0] != f.shape[0] or f0_tgt.shape[1] != 1 or f0_tgt.shape[2] != n_t + 1 or n_t > f.shape[1]:
+        raise ValueError(f'f0_yin_loss: f0_tgt must be [B, 1, {n_t + 1}] for this signal, got {tuple(f0_tgt.shape)}')
+    f = f[:, :n_t]                                         # YIN has one frame more when T is no multiple of hop
+    t = f0_tgt[:, 0, :-1].detach().to(f.dtype)
+    v = ((t > 0) & (f.detach() > 0)).to(f.dtype)
+    e = (f - t) / scale
+    return ((v * e * e).sum() / v.sum().clamp(min=1.0)).reshape(1)
+
+
 # ------------------------------------------------------------------------------- contrastive
 class _ContrastiveFn(Function):
     @staticmethod

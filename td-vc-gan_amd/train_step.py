@@ -3,7 +3,8 @@
 Mirrors the loop body of the reference's train.py:209-521 (D-step :259-316, G-step :320-510,
 loss assembly :477-482, optimizers :188-189; cycle-reconstruction branch :344-361 when lambda_rec > 0)
 for the configuration space of the shipped YAMLs,
-minus the CREPE-backed F0 term (:429-470, torchcrepe unavailable: SURVEY §8c) and minus work
+minus the CREPE-backed F0 term (:429-470, torchcrepe unavailable: SURVEY §8c; the reference's commented YIN route to the same
+term, :438/:441/:466-467, is available as the opt-in `f0_loss='yin'`) and minus work
 that reaches no parameter update:
   Q3  the D-step's generator forward runs without a graph (the reference back-propagates into G
       through the sub-scale heads and then discards those gradients);
@@ -48,14 +49,18 @@ class StepConfig:
     d_step_interval: int = 1            # train.py:259
     g_step_interval: int = 1            # train.py:320
     freeze_subnets: tuple = ()          # train.py:195-197: ('encoder',) -> G.encoder parameters get requires_grad = False
+    f0_loss: str = None                 # None: lambda_f0 reaches no loss; 'yin': lambda_f0 * losses.f0_yin_loss(fake, batch['f0_conv'])
 
     @staticmethod
-    def from_hparams(train: dict) -> 'StepConfig':
+    def from_hparams(train: dict, f0_loss: str = None) -> 'StepConfig':
         """Build from the `train` document of a reference YAML (config/*.yaml). `lambda_f0` (the CREPE-backed F0 term,
-        train.py:429-470) is excluded by contract (torchcrepe is not available: SURVEY §8c) and only warns; a sub-network
+        train.py:429-470) is excluded by contract (torchcrepe is not available: SURVEY §8c) and only warns, unless the caller
+        opts into the soft-YIN route with f0_loss='yin' (losses.f0_yin_loss; the step then needs batch['f0_conv']); a sub-network
         name in `freeze_subnets` other than 'encoder' is ignored by the reference too (train.py:195)."""
         g = train.get
-        if float(g('lambda_f0', 0) or 0) != 0:
+        if f0_loss not in (None, 'yin'):
+            raise ValueError(f"f0_loss must be None or 'yin', got {f0_loss!r}")
+        if f0_loss is None and float(g('lambda_f0', 0) or 0) != 0:
             import warnings
             warnings.warn('lambda_f0 != 0: the CREPE-backed F0 loss term (train.py:429-470) is not part of this path '
                           '(torchcrepe unavailable); the iteration runs without it', stacklevel=2)
@@ -71,7 +76,7 @@ class StepConfig:
                           grad_max_norm_d=(float(g('grad_max_norm_D')) if g('grad_max_norm_D') is not None else None),
                           grad_max_norm_g=(float(g('grad_max_norm_G')) if g('grad_max_norm_G') is not None else None),
                           d_step_interval=int(g('D_step_interval', 1) or 1), g_step_interval=int(g('G_step_interval', 1) or 1),
-                          freeze_subnets=tuple(g('freeze_subnets') or ()))
+                          freeze_subnets=tuple(g('freeze_subnets') or ()), f0_loss=f0_loss)
 
 
 class TrainStep:
@@ -81,6 +86,8 @@ class TrainStep:
         self.grad_sync = grad_sync            # parallel.GradSync or None
         self.comm_events = None               # set to [] to record (backward done, all-reduce joined) event pairs per optimizer step
         self.iter_count = 0                   # train.py:211: the step intervals count iterations from 0
+        if cfg.f0_loss not in (None, 'yin'):
+            raise ValueError(f"StepConfig.f0_loss must be None or 'yin', got {cfg.f0_loss!r}")
         if 'encoder' in cfg.freeze_subnets:   # train.py:195-197
             for p_ in G.encoder.parameters():
                 p_.requires_grad = False
@@ -182,6 +189,10 @@ class TrainStep:
         G, D, c = self.G, self.D, self.cfg
         real = batch['signal_real']
         B = real.shape[0]
+        want_f0 = c.f0_loss == 'yin' and c.lambda_f0 != 0
+        if want_f0 and 'f0_conv' not in batch:
+            raise ValueError("f0_loss='yin' with lambda_f0 != 0 needs batch['f0_conv']: the [B, 1, T/64 + 1] F0 track in Hz that the "
+                             "excitation batch['c_f0_conv'] was made from")
         D.arena.wgrad_enabled = False                     # Q5
         if self.C is not None:
             self.C.arena.wgrad_enabled = False            # the classifier's own grads from the G-step are dead work too
@@ -301,6 +312,10 @@ class TrainStep:
                 l_cls = LS.cross_entropy_loss(self.C(emb_real), batch['label_src'])
                 log['G_loss_lat_cls'] = l_cls.detach()
                 total = total + c.lambda_latcls * l_cls
+            if want_f0:                 # train.py:438, :441, :466-467 (the YIN route), tag as in train.py:501
+                l_f0 = LS.f0_yin_loss(fake, batch['f0_conv'])
+                log['g_loss_f0'] = l_f0.detach()
+                total = total + c.lambda_f0 * l_f0
             if emb_cor is not None:
                 l_con = LS.contrastive_loss(emb_real, emb_cor, num_negatives=c.n_neg, temp=0.1, idx_x=idx_x, idx_y=idx_y)
                 log['G_loss_cont_emb'] = l_con.detach()
