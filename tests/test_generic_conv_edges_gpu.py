@@ -2,7 +2,8 @@
 conv_wgrad_kernel<MODE,M_REP,J> / conv_wgrad_scalar_kernel, the small-group kernels at their boundary, and the slab folds
 (immediate and deferred) that end every weight-grad call.
 
-The stride-1 lean family has test_kernel_instances_gpu.py; this file gives the generic family the same treatment:
+The stride-1 lean family has test_kernel_instances_gpu.py (its weight-grad kernels: test_lean_wgrad_edges_gpu.py, which drives the
+Edge class below); this file gives the generic family the same treatment:
 
   * every tile of launch_conv_gemm, pinned through tdvc_debug_force_gemm_tile, at small ragged shapes with NaN-poisoned LDS;
   * sequence lengths that are no multiple of 4, channel counts per group that are no multiple of 4 / 16, out_pad > 0,
@@ -105,26 +106,35 @@ def _conv64(h, w, b, geom):
     return F.conv1d(h, w, b, stride=s, padding=p, dilation=d, groups=g)
 
 
-def _buf(B, Cc, T, dev, views, src=None):
+def _buf(B, Cc, T, dev, views, src=None, unaligned=False):
     """(whole buffer, operand view): SENT-filled; with `views` the operand is the channel slice [:, :Cc] of a [B, Cc + 3, T] buffer
-    (a batch stride wider than contiguous and, for odd T, planes that are not 16-byte aligned)."""
-    whole = torch.full((B, Cc + (3 if views else 0), T), SENT, dtype=torch.float32, device=dev)
-    v = whole[:, :Cc]
+    (a batch stride wider than contiguous and, for odd T, planes that are not 16-byte aligned); with `unaligned` it lives one
+    float into a flat buffer (contiguous rows, nothing 16-byte aligned; the float in front stays SENT)."""
+    if unaligned:
+        assert not views
+        whole = torch.full((B * Cc * T + 1,), SENT, dtype=torch.float32, device=dev)
+        v = whole[1:].view(B, Cc, T)
+    else:
+        whole = torch.full((B, Cc + (3 if views else 0), T), SENT, dtype=torch.float32, device=dev)
+        v = whole[:, :Cc]
     if src is not None:
         v.copy_(src.to(dev))
     return whole, v
 
 
 def _spare_intact(whole, Cc):
+    if whole.dim() == 1:
+        return bool(whole[0] == SENT)
     return whole.shape[1] == Cc or bool((whole[:, Cc:] == SENT).all())
 
 
-def elem_check(got, ref, A, n):
-    """-> (worst err / bound over the elements with A > 0, number of elements with A == 0 that differ from fp32(ref))."""
+def elem_check(got, ref, A, n, slack=8):
+    """-> (worst err / bound over the elements with A > 0, number of elements with A == 0 that differ from fp32(ref)).
+    `slack`: the roundings outside the summation the bound allows for (8; 12 with a FiLM prologue, Edge's docstring)."""
     got = got.detach().cpu()
     assert got.shape == ref.shape, (got.shape, ref.shape)
     err = (got.double() - ref).abs()
-    bound = (n + 8) * U * A + 2.0 ** -22 * ref.abs()
+    bound = (n + slack) * U * A + 2.0 ** -22 * ref.abs()
     zero = A == 0
     inexact = int((got[zero] != ref[zero].float()).sum())
     ratio = float((err[~zero] / bound[~zero]).max()) if bool((~zero).any()) else 0.0
@@ -135,14 +145,30 @@ def elem_check(got, ref, A, n):
 
 class Edge:
     """One conv geometry through tdvc_conv_fwd / _dgrad / _wgrad against float64 CPU autograd (the module docstring has the rules).
-    fwd() must run first: a post-LeakyReLU layer takes its backward mask from the GPU's own stored output, as the product does."""
+    fwd() must run first: a post-LeakyReLU layer takes its backward mask from the GPU's own stored output, as the product does.
 
-    def __init__(self, geom, dev, generic=0, B=3, pre=0, post=0, add=False, views=False, w_cin=0, w_cin_off=0):
+    Options beyond the geometry (the defaults are the plain case):
+      with_db=False  dbias = NULL: db must stay db0 bit for bit and no bias-gradient kernel may run;
+      wt=True        the slot carries the [Cin][Cout][K] weight copy the lean input-grad kernel reads;
+      unaligned=True x, dy, y, dx (and add / FiLM operands) start 4 bytes into flat buffers: contiguous rows, nothing 16-byte aligned;
+      film=True      (1x1 convs) the input prologue is FiLM + LeakyReLU, x' = lrelu(h * (1 + gamma) + beta), with gb = [gamma planes,
+                     beta planes] as XF_FILM_LRELU's aux operand, and the input-grad runs the FiLM epilogue (dh, dgamma, dbeta).
+    The FiLM bound: the GPU forms x' in fp32 from fp32 h, gamma, beta: 1 + gamma, the product and the sum are three roundings, each at
+    most 2^-24 of a partial result no larger than H = |h| (1 + |gamma|) + |beta|, so |x'_gpu - x'| <= 3 * 2^-24 * H on either side of
+    the kink. An element within that distance of 0 may take the other LeakyReLU branch: the branches differ by 0.8 |h2| there, at most
+    0.8 * 3 * 2^-24 * H more. Together < 3 * 2^-23 * H per element, i.e. 3 more units of 2^-23 * A when A is computed from H instead of
+    |x'|. So the FiLM cases take A from H and n + 12 for n + 8. The input-grad's mask is discontinuous at the kink; the seeded data is
+    asserted to hold no element that close to it, so both sides take the same branch everywhere."""
+
+    def __init__(self, geom, dev, generic=0, B=3, pre=0, post=0, add=False, views=False, w_cin=0, w_cin_off=0,
+                 with_db=True, wt=False, unaligned=False, film=False):
         ops, L, arena = _mods()
         (name, cin, cout, k, s, p, d, g, reflect, transposed, out_pad, T) = geom
         assert not (add and post), 'the backward mask of a post-activated layer is its stored output: no running sum on top'
         self.geom, self.dev, self.generic, self.B, self.pre, self.post, self.views = geom, dev, generic, B, pre, post, views
         self.cin, self.cout, self.T = cin, cout, T
+        self.with_db, self.film, self.unaligned, self.slack = with_db, film, unaligned, 12 if film else 8
+        assert not film or (k == 1 and not pre), 'FiLM is the prologue of the 1x1 conv behind it, in place of the plain LeakyReLU'
         self.out_scale, self.add_scale = (0.5, 0.75) if add else (1.0, 1.0)
         gen = torch.Generator().manual_seed(sum(map(ord, name)))
         rnd = lambda *sh: torch.randn(*sh, generator=gen).float()      # fp32 values: the reference reads the same numbers
@@ -155,18 +181,25 @@ class Edge:
         self.add_y = rnd(B, cout, self.tout) if add else None
         self.add_x = rnd(B, cin, T) if add else None
         self.dw0, self.db0 = rnd(*wshape), rnd(cout)
+        self.gb = rnd(B, 2 * cin, T) * 0.5 if film else None      # drawn last: the other tensors of a case do not depend on the option
         # n of the bound: reduction length per tensor
         self.n = dict(y=cin // g * k, dx=cout // g * k, dw=B * self.tout, db=B * self.tout)
         f = lambda t: t.to(dev).contiguous()
         self.wd, self.bd, self.dw, self.db = f(self.w), f(self.b), f(self.dw0), f(self.db0)
-        self.spec.slot = arena.ConvSlot(self.wd.data_ptr(), self.bd.data_ptr(), self.dw.data_ptr(), self.db.data_ptr(), True, None, 0)
-        self.x_whole, self.xv = _buf(B, cin, T, dev, views, self.x)
-        self.dy_whole, self.dyv = _buf(B, cout, self.tout, dev, views, self.cot)
-        self.y_whole, self.yv = _buf(B, cout, self.tout, dev, views)
-        self.dx_whole, self.dxv = _buf(B, cin, T, dev, views)
-        self.addy_v = _buf(B, cout, self.tout, dev, views, self.add_y)[1] if add else None
-        self.addx_v = _buf(B, cin, T, dev, views, self.add_x)[1] if add else None
+        self.wtd = self.wd.permute(1, 0, 2).contiguous() if wt else None      # [Cin (or w_cin)][Cout][K]
+        self.spec.slot = arena.ConvSlot(self.wd.data_ptr(), self.bd.data_ptr(), self.dw.data_ptr(), self.db.data_ptr(), True, None,
+                                        self.wtd.data_ptr() if wt else 0)
+        self.x_whole, self.xv = _buf(B, cin, T, dev, views, self.x, unaligned)
+        self.dy_whole, self.dyv = _buf(B, cout, self.tout, dev, views, self.cot, unaligned)
+        self.y_whole, self.yv = _buf(B, cout, self.tout, dev, views, None, unaligned)
+        self.dx_whole, self.dxv = _buf(B, cin, T, dev, views, None, unaligned)
+        self.addy_v = _buf(B, cout, self.tout, dev, views, self.add_y, unaligned)[1] if add else None
+        self.addx_v = _buf(B, cin, T, dev, views, self.add_x, unaligned)[1] if add else None
         self.x_xf = ops._xf(L.XF_LRELU if pre else L.XF_NONE)
+        if film:
+            self.gbv = _buf(B, 2 * cin, T, dev, views, self.gb, unaligned)[1]
+            self.dgb_whole, self.dgbv = _buf(B, 2 * cin, T, dev, views, None, unaligned)
+            self.x_xf = ops._xf(L.XF_FILM_LRELU, aux=self.gbv)
         self.names = {}
 
     def _call(self, what, fn):
@@ -188,20 +221,30 @@ class Edge:
         y = self.yv.detach().cpu()
         # float64 reference, and the same computation on absolute values for the bound
         xr, wr, br = (t.double().requires_grad_(True) for t in (self.x, self.w, self.b))
-        z = _conv64(F.leaky_relu(xr, SLOPE) if self.pre else xr, wr[:, self.win], br, self.geom)
+        if self.film:
+            gbr = self.gb.double().requires_grad_(True)
+            h2 = xr * (1 + gbr[:, :self.cin]) + gbr[:, self.cin:]
+            H = self.x.double().abs() * (1 + self.gb.double()[:, :self.cin].abs()) + self.gb.double()[:, self.cin:].abs()
+            assert bool((h2.detach().abs() > 3 * U * H).all()), 'an element of the seeded data sits on the LeakyReLU kink: reseed the case'
+        z = _conv64(F.leaky_relu(h2, SLOPE) if self.film else F.leaky_relu(xr, SLOPE) if self.pre else xr, wr[:, self.win], br, self.geom)
         self.act = torch.where(y > 0, 1.0, SLOPE).double() if self.post else torch.ones_like(z)      # out_scale > 0 and no add with post
         yr = self.out_scale * z * self.act
         if self.add_y is not None:
             yr = yr + self.add_y.double()
         (yr * self.cot.double()).sum().backward()
         dy_eff = (self.cot.double() * self.out_scale * self.act).abs()
-        ha = (F.leaky_relu(xr.detach(), SLOPE) if self.pre else xr.detach()).abs().requires_grad_(True)
+        ha = (H if self.film else F.leaky_relu(xr.detach(), SLOPE) if self.pre else xr.detach()).abs().requires_grad_(True)
         wa = self.w.double().abs().requires_grad_(True)
         za = _conv64(ha, wa[:, self.win], None, self.geom)
         (za * dy_eff).sum().backward()
         self.ref = dict(y=yr.detach(), dx=xr.grad + (self.add_scale * self.add_x.double() if self.add_x is not None else 0),
                         dw=self.dw0.double() + wr.grad, db=self.db0.double() + br.grad)
         self.A = dict(y=self.out_scale * za.detach(), dx=ha.grad, dw=wa.grad, db=dy_eff.sum((0, 2)))
+        if self.film:      # dh = g m (1 + gamma), dgamma = g m h, dbeta = g m with g = W^T dy and the mask m <= 1
+            gam = self.gb.double()[:, :self.cin].abs()
+            self.ref['dgb'], self.n['dgb'] = gbr.grad, self.n['dx']
+            self.A['dgb'] = torch.cat([ha.grad * self.x.double().abs(), ha.grad], 1)
+            self.A['dx'] = ha.grad * (1 + gam)
         assert _spare_intact(self.y_whole, self.cout), 'forward wrote into the spare channels behind y'
         return self._bars('y', self.yv)
 
@@ -211,6 +254,13 @@ class Edge:
 
     def dgrad(self):
         ops, L, _ = _mods()
+        if self.film:
+            self._call('dgrad', lambda: ops.conv_dgrad_raw(self.spec, self.dyv, self.dy_xf(), self.T, L.DG_FILM, x_in=self.xv, gb=self.gbv, dgb=self.dgbv,
+                                                            add=self.addx_v, add_scale=self.add_scale, out=self.dxv))
+            assert _spare_intact(self.dx_whole, self.cin) and _spare_intact(self.dgb_whole, 2 * self.cin), 'input-grad wrote outside dx / dgb'
+            out = self._bars('dx', self.dxv)
+            out.update(self._bars('dgb', self.dgbv))
+            return out
         self._call('dgrad', lambda: ops.conv_dgrad_raw(self.spec, self.dyv, self.dy_xf(), self.T, L.DG_MASK_LRELU if self.pre else L.DG_PLAIN,
                                                         x_in=self.xv if self.pre else None, add=self.addx_v, add_scale=self.add_scale, out=self.dxv))
         assert _spare_intact(self.dx_whole, self.cin), 'input-grad wrote into the spare channels behind dx'
@@ -229,7 +279,7 @@ class Edge:
         guard = torch.full((lead + self.query // 4 + 64,), SENT, dtype=torch.float32, device=self.dev)
         dyx = self.dy_xf()
         a = L.ConvWgradArgs(self.xv.data_ptr(), self.xv.stride(0), self.x_xf, self.dyv.data_ptr(), self.dyv.stride(0), dyx,
-                            self.dw.data_ptr() if with_dw else None, self.db.data_ptr(), guard.data_ptr() + 4 * lead if nbytes else None, nbytes)
+                            self.dw.data_ptr() if with_dw else None, self.db.data_ptr() if self.with_db else None, guard.data_ptr() + 4 * lead if nbytes else None, nbytes)
         st = torch.cuda.current_stream(self.dev).cuda_stream
 
         def run():
@@ -246,11 +296,15 @@ class Edge:
         assert rc == 0, (rc, _mods()[1].lib().tdvc_last_error())
         assert self.guard_ok, f'weight-grad wrote outside its {self.query}-byte workspace'
         out = self._bars('dw', self.dw)
+        if not self.with_db:      # dbias = NULL: the bias gradient buffer must not be touched
+            assert torch.equal(self.db.cpu(), self.db0), 'dbias = NULL, but the bias gradient buffer was written'
+            assert 'conv_bias_grad_kernel' not in self.names['wgrad'], sorted(self.names['wgrad'])
+            return out
         out.update(self._bars('db', self.db))
         return out
 
     def _bars(self, key, got):
-        ratio, inexact = elem_check(got, self.ref[key], self.A[key], self.n[key])
+        ratio, inexact = elem_check(got, self.ref[key], self.A[key], self.n[key], self.slack)
         return {key: dict(rel=rel_l2(got, self.ref[key]), ratio=ratio, inexact=inexact)}
 
     def run_all(self):
