@@ -383,6 +383,26 @@ int tdvc_yin_soft_bwd(const float* x, int64_t x_bs, int32_t B, int32_t T, int32_
                       float threshold, float sample_rate, const float* gy, float* dx, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* Random parametric EQ of the data pipeline (util/contentvec/audio_corruption.py random_eq + util.eq_rms_signals, which is all that
+ * data/dataset.py:68-86 corrupt_audio returns): csrc/audio_eq.hip.
+ *
+ * tdvc_peq_sos: the reference's params2sos in float64 on the device. gains_db, q fp32 [B][n_bands] (dB, Q factor), fc float64
+ * [n_bands] in Hz, sos float64 [B][n_bands][6] in scipy's layout b0 b1 b2 a0 a1 a2 with a0 = 1. Band 0 is the low shelf, band
+ * n_bands-1 the high shelf, the bands between are peaking filters (RBJ cookbook), with the reference's max(fc, 2.0) and
+ * A = max(0, sqrt(g)) guards. TDVC_EINVAL for n_bands < 2. One launch, no host round trip, graph-capturable.
+ *
+ * tdvc_sos_filter: y[b] = the cascade sos[b] (float64 [B][n_sections][6], a0 = 1, one set per row) applied to x[b] from a zero
+ * state, = scipy.signal.sosfilt(sos[b], x[b]) computed in float64 and rounded once to fp32. x, y fp32 [B][T], last axis dense,
+ * rows x_bs / y_bs elements apart. match_rms != 0 multiplies each row by rms(x_row) / (rms(y_row) + 1e-8) before that rounding
+ * (both sums of squares in float64, fixed order). One launch, one block per row, the serial dependence over T broken by a
+ * chunked state carry; no atomics, bit-identical from call to call. 1 <= n_sections <= 16 and T >= 1, TDVC_EUNSUPPORTED
+ * otherwise; B == 0 or T == 0 is a no-op. The workspace query returns 0 today (workspace may be NULL). */
+int tdvc_peq_sos(const float* gains_db, const float* q, const double* fc, int32_t n_bands, double sample_rate, int32_t B,
+                 double* sos, void* stream);
+size_t tdvc_sos_filter_workspace(int32_t B, int32_t T, int32_t n_sections);
+int tdvc_sos_filter(const float* x, int64_t x_bs, const double* sos, int32_t B, int32_t T, int32_t n_sections, int32_t match_rms,
+                    float* y, int64_t y_bs, void* workspace, size_t workspace_bytes, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X, const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

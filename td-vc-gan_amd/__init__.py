@@ -3,7 +3,8 @@
 Drop-in surface (same names / signatures / state_dict keys as the reference):
     Generator, CollaborativeMultibandDiscriminator, ConditionalInstanceNorm, LatentClassifier,
     losses.{multiscale_spec_loss, multiscale_feat_loss, contrastive_loss}, TrainStep, and the YIN pitch tracker of util/yin.py as
-    yin_f0 / track_f0 (pitch.py).
+    yin_f0 / track_f0 (pitch.py), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
+    EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -18,12 +19,14 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
     if name in ('yin_f0', 'track_f0'):
         return getattr(importlib.import_module(f'{__name__}.pitch'), name)
+    if name in ('peq_sos', 'sos_filter', 'random_eq', 'corrupt_audio', 'device_batch'):
+        return getattr(importlib.import_module(f'{__name__}.corrupt'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

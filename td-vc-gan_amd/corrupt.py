@@ -1,0 +1,170 @@
+"""Signal corruption on the device: the `signal_corrupted` member of a training batch, which the reference makes in DataLoader
+workers with scipy (data/dataset.py:68-86 corrupt_audio -> util/contentvec/audio_corruption.py random_eq -> util.eq_rms_signals).
+
+corrupt_audio first calls the Praat formant / pitch perturbation and then overwrites its result: line 84 filters `signal`, not the
+Praat output. What it returns is therefore a random ten-band parametric EQ of the clean signal, RMS-matched to it, and that is
+what this module computes: `peq_sos` (tdvc_peq_sos, the reference's params2sos in float64 on the device), `sos_filter`
+(tdvc_sos_filter, per-row float64 biquad cascades parallel over time, csrc/audio_eq.hip) and `random_eq` / `corrupt_audio` on top.
+`device_batch` builds the whole batch dict TrainStep reads from a device waveform batch and labels. Nothing here is differentiable.
+"""
+import math
+
+import torch
+
+from . import _lib as L
+from .infer import shift_f0
+from .pitch import track_f0
+from .util import f0_to_excitation
+
+Q_MIN, Q_MAX = 2.0, 5.0
+GAIN_DB = 12.0
+N_BANDS = 10
+FC = tuple(math.exp(math.log(60.0) + (math.log(7600.0) - math.log(60.0)) * k / (N_BANDS - 1)) for k in range(N_BANDS))
+F0_HOP = 64
+
+_fc_cache = {}
+
+
+def _default_fc(device):
+    """The reference's ten log-spaced centres 60 .. 7600 Hz as a float64 device tensor, uploaded once per device (so that a later
+    call copies nothing from the host and can be captured into a graph)."""
+    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _fc_cache:
+        _fc_cache[key] = torch.tensor(FC, dtype=torch.float64).to(device)
+    return _fc_cache[key]
+
+
+def _need_device(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise L.TdvcError(f'{what}: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
+
+
+def peq_sos(gains_db, q, sample_rate=16000, fc=None):
+    """Second-order sections of a parametric EQ: gains_db, q [B, n] (dB, Q factor) -> float64 [B, n, 6] on the device, rows
+    b0 b1 b2 1 a1 a2. Band 0 is a low shelf, band n-1 a high shelf, the others peaking filters (the reference's params2sos).
+    fc: n centre frequencies in Hz, default the reference's ten log-spaced centres."""
+    _need_device(gains_db, 'peq_sos')
+    dev = gains_db.device
+    g = gains_db.detach().to(torch.float32).contiguous()
+    qq = q.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if g.dim() != 2 or qq.shape != g.shape:
+        raise ValueError('peq_sos: gains_db and q must both be [B, n_bands]')
+    B, n = g.shape
+    fc_t = _default_fc(dev) if fc is None else torch.as_tensor(fc, dtype=torch.float64).to(dev).contiguous()
+    if fc_t.shape != (n,):
+        raise ValueError(f'peq_sos: {n} bands need {n} centre frequencies, got {tuple(fc_t.shape)}')
+    if n < 2:
+        raise ValueError('peq_sos: needs at least two bands (a low and a high shelf)')
+    sos = torch.empty(B, n, 6, dtype=torch.float64, device=dev)
+    L.check(L.lib().tdvc_peq_sos(g.data_ptr(), qq.data_ptr(), fc_t.data_ptr(), n, float(sample_rate), B, sos.data_ptr(),
+                                 torch.cuda.current_stream(dev).cuda_stream))
+    return sos
+
+
+def sos_filter(signal, sos, match_rms=False):
+    """signal [T], [B, T] or [B, 1, T] (fp32, device) through the biquad cascades sos [B, S, 6] (float64, scipy's layout, a0 = 1;
+    one cascade per row, zero initial state) -> the same shape: scipy.signal.sosfilt per row, computed in float64 and rounded once.
+    match_rms=True scales each row to the RMS of its input row (util.eq_rms_signals) before that rounding. Rows may be strided;
+    only a signal whose last axis is not dense is copied."""
+    _need_device(signal, 'sos_filter')
+    _need_device(sos, 'sos_filter')
+    if signal.dim() not in (1, 2, 3) or (signal.dim() == 3 and signal.shape[1] != 1):
+        raise ValueError('sos_filter: signal must be [T], [B, T] or [B, 1, T]')
+    x = signal.detach().float()
+    shape, T = x.shape, x.shape[-1]
+    x2 = x[:, 0] if x.dim() == 3 else x.reshape(1, T) if x.dim() == 1 else x
+    if T > 1 and x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    B = x2.shape[0]
+    x_bs = x2.stride(0) if B > 1 else T
+    if x_bs < 0:
+        x2, x_bs = x2.contiguous(), T
+    sos = sos.detach().to(torch.float64).contiguous()
+    if sos.dim() == 2:
+        sos = sos.unsqueeze(0)
+    if sos.dim() != 3 or sos.shape[0] != B or sos.shape[2] != 6:
+        raise ValueError(f'sos_filter: sos must be [B = {B}, n_sections, 6], got {tuple(sos.shape)}')
+    S = sos.shape[1]
+    lib = L.lib()
+    y = torch.empty(B, T, dtype=torch.float32, device=x.device)      # the kernel writes every element
+    nbytes = lib.tdvc_sos_filter_workspace(B, T, S)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    rc = lib.tdvc_sos_filter(x2.data_ptr(), x_bs, sos.data_ptr(), B, T, S, int(bool(match_rms)), y.data_ptr(), T,
+                             ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(x.device).cuda_stream)
+    if rc == L.EUNSUPPORTED:
+        raise ValueError(f'sos_filter: {lib.tdvc_last_error().decode()}')
+    L.check(rc)
+    return y.reshape(shape)
+
+
+def random_eq(signal, sample_rate=16000, gains_db=None, z=None, generator=None, match_rms=True):
+    """Random parametric EQ of signal [T], [B, T] or [B, 1, T] (reference: audio_corruption.random_eq, per row): ten bands at the
+    log-spaced centres, gains G ~ U(-12, 12) dB, Q = 2 * 2.5^z with z ~ U(0, 1). The draws are optional inputs, gains_db and z
+    [B, 10]; by default they are drawn on the device with `generator`. No host synchronisation anywhere in the call."""
+    _need_device(signal, 'random_eq')
+    dev = signal.device
+    B = 1 if signal.dim() == 1 else signal.shape[0]
+    if gains_db is None:
+        gains_db = (torch.rand(B, N_BANDS, device=dev, generator=generator) * 2.0 - 1.0) * GAIN_DB
+    if z is None:
+        z = torch.rand(B, N_BANDS, device=dev, generator=generator)
+    gains_db, z = gains_db.to(dev), z.to(dev)
+    if gains_db.shape != (B, N_BANDS) or z.shape != (B, N_BANDS):
+        raise ValueError(f'random_eq: gains_db and z must be [{B}, {N_BANDS}]')
+    q = Q_MIN * torch.pow(Q_MAX / Q_MIN, z.double())      # float64 until tdvc_peq_sos takes it: one rounding to fp32
+    return sos_filter(signal, peq_sos(gains_db, q, sample_rate), match_rms=match_rms)
+
+
+def corrupt_audio(signal, sample_rate=16000, gains_db=None, z=None, generator=None):
+    """What data/dataset.py:68 corrupt_audio returns: random_eq of the clean signal, RMS-matched to it. (The Praat step before it
+    in the reference is overwritten by line 84 and contributes nothing.)"""
+    return random_eq(signal, sample_rate, gains_db=gains_db, z=z, generator=generator, match_rms=True)
+
+
+def pair_targets(label_src, num_spk, conversion=True, perm=None, generator=None):
+    """In-batch target pairing of train.py:215-226 on the device: perm (a random permutation of the batch when converting, the
+    identity with no_conv), label_tgt = label_src[perm] and the two one-hot codes. -> (perm, label_tgt, c_src, c_tgt)"""
+    B, dev = label_src.shape[0], label_src.device
+    if perm is None:
+        perm = torch.randperm(B, device=dev, generator=generator) if conversion else torch.arange(B, device=dev)
+    perm = perm.to(device=dev, dtype=torch.int64)
+    label_tgt = label_src[perm]
+    onehot = lambda l: torch.nn.functional.one_hot(l, num_spk).to(torch.float32)
+    return perm, label_tgt, onehot(label_src), onehot(label_tgt)
+
+
+@torch.no_grad()
+def device_batch(signal_real, label_src, num_spk, conversion=True, generator=None, sample_rate=16000, gains_db=None, z=None,
+                 perm=None, noise_src=None, noise_conv=None, start_phase_src=None, start_phase_conv=None):
+    """The batch dict of train.py:214-256 from a device waveform batch signal_real [B, 1, T] and labels label_src [B] (int64):
+    signal_corrupted = corrupt_audio(signal_real); the in-batch target pairing; F0 tracks from track_f0 (YIN), shifted towards the
+    target speaker with infer.shift_f0 when converting; the two excitations from util.f0_to_excitation. Returns the keys TrainStep
+    reads: signal_real, signal_corrupted, label_src, label_tgt, c_src, c_tgt, c_f0_src, c_f0_conv, f0_conv, perm.
+    Every random draw is an optional input (gains_db, z [B, 10]; perm [B]; noise_* = (voiced, unvoiced) normal tensors [B, 1, T];
+    start_phase_* 1-element tensors), drawn on the device with `generator` otherwise. T must be a multiple of the F0 hop (64)."""
+    _need_device(signal_real, 'device_batch')
+    if signal_real.dim() != 3 or signal_real.shape[1] != 1:
+        raise ValueError('device_batch: signal_real must be [B, 1, T]')
+    B, _, T = signal_real.shape
+    if T % F0_HOP:
+        raise ValueError(f'device_batch: T = {T} is not a multiple of the F0 hop {F0_HOP}')
+    dev = signal_real.device
+    signal_real = signal_real.float()
+    label_src = label_src.to(device=dev, dtype=torch.int64)
+    perm, label_tgt, c_src, c_tgt = pair_targets(label_src, num_spk, conversion, perm, generator)
+    corrupted = corrupt_audio(signal_real, sample_rate, gains_db=gains_db, z=z, generator=generator)
+    f0_src = track_f0(signal_real, hop=F0_HOP, sample_rate=sample_rate)
+    f0_conv = shift_f0(f0_src, f0_src[perm]) if conversion else f0_src
+
+    def draws(noise, phase):
+        if noise is None:
+            noise = (torch.randn(B, 1, T, device=dev, generator=generator), torch.randn(B, 1, T, device=dev, generator=generator))
+        if phase is None:
+            phase = torch.rand(1, device=dev, generator=generator) * (2 * math.pi)
+        return noise, phase
+    n_c, p_c = draws(noise_conv, start_phase_conv)
+    n_s, p_s = draws(noise_src, start_phase_src)
+    c_f0_conv = f0_to_excitation(f0_conv, F0_HOP, sampling_rate=sample_rate, noise=n_c, start_phase=p_c)
+    c_f0_src = f0_to_excitation(f0_src, F0_HOP, sampling_rate=sample_rate, noise=n_s, start_phase=p_s)
+    return dict(signal_real=signal_real, signal_corrupted=corrupted, label_src=label_src, label_tgt=label_tgt, c_src=c_src, c_tgt=c_tgt,
+                c_f0_src=c_f0_src, c_f0_conv=c_f0_conv, f0_conv=f0_conv, perm=perm)
