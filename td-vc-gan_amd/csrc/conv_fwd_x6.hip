@@ -1,6 +1,6 @@
 // Forward of a 3-tap stride-1 'same' conv with 65..160 input channels (FiLM's cond_var.2, model/generator.py:86-92: 136 -> 2C,
 // ~9 % of the train step) on the bf16 matrix pipe at fp32 accuracy -- the split-bf16 x6 scheme of conv_wgrad_x6.hip (three
-// exact bf16 pieces per operand, six piece products on v_mfma_f32_16x16x32_bf16, fp32 accumulation).
+// exact bf16 pieces per operand, six piece products on v_mfma_f32_16x16x32_bf16, fp32 accumulation: split_bf16.h).
 //     y[co][t] = bias[co] + sum_{ci,j} W[co][ci][j] * x'[ci][t + j - 1],      x' = LeakyReLU(x) (or x)
 // K of the product is (tap, input channel): a lane's 8 consecutive k values are 8 consecutive CHANNELS at one time step, so the
 // activation tile is held TRANSPOSED in LDS ([time][channel], channel fastest). The transposition happens in registers on the
@@ -15,15 +15,12 @@
 // 64 (w & 1) .. + 63 x half of the output-channel tiles. Loads of chunk c + 1 are in flight during the MFMAs of chunk c.
 #include "conv_common.h"
 #include "api_util.h"
+#include "split_bf16.h"
+#include <initializer_list>
 
 PROF_DEFINE(tdvc_debug_fwdx6_prof)
 
 namespace tdvc {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct FwdX6P {
   const float* x; long x_bs;            // [B][Cin][T]
@@ -36,40 +33,88 @@ struct FwdX6P {
 
 constexpr int FX_NT = 128;              // steps per block
 constexpr int FX_CP = 160;              // padded channel count of the weight planes (5 chunks of 32)
-constexpr int FX_RS = 32;               // bf16 row length of both LDS images: 64 B, no padding; the 16-byte slot q of row r lives at slot q ^ ((r >> 1) & 3)
 constexpr int FX_PR = 34;               // rows of one phase plane: window index s = position - (n0 - 4) = 4 row + phase, s in [3, 132]
-constexpr int FX_XPL = 4 * FX_PR * FX_RS;   // one piece of the activation tile: [phase][row][FX_RS]
+constexpr int FX_XPL = 4 * FX_PR * X6_RS;   // one piece of the activation tile: [phase][row][X6_RS]
 constexpr int FX_WREC = 3 * 32 * 3 * 4;     // 16-byte vectors of one weight record (32 output channels x one chunk): [piece][co][tap][4]
+constexpr int FX_ES = 140;              // row stride of the fused kernel's excitation tile: window [n0 - 4, n0 + 132) + 4 (rows 16-byte aligned)
+// dynamic LDS of a block of MT output channels (bf16 elements; both images start on multiples of 8 rows):
+//   xt [3 pieces][4 phases][FX_PR][X6_RS] | ws [3 pieces][3 taps][MT][X6_RS] (swizzled rows) | fused kernel only: es [8][FX_ES] fp32
+constexpr int FX_WS_OFF = 3 * FX_XPL;
+constexpr int fx_es_off(int MT) { return FX_WS_OFF + 3 * MT * 3 * X6_RS; }
+constexpr int fx_lds_bytes(int MT, bool exc) { return fx_es_off(MT) * 2 + (exc ? 8 * FX_ES * 4 : 0); }
 
-// exact: f = h + m + l, each piece the UPPER half of its word (l's lower half is zero by construction: 24 significant bits in all;
-// it is left unmasked and dropped by the pack)
-__device__ __forceinline__ void split1(const float f, unsigned& h, unsigned& m, unsigned& l) {
-  h = __builtin_bit_cast(unsigned, f) & 0xffff0000u;
-  const float r1 = f - __builtin_bit_cast(float, h);
-  m = __builtin_bit_cast(unsigned, r1) & 0xffff0000u;
-  const float r2 = r1 - __builtin_bit_cast(float, m);
-  l = __builtin_bit_cast(unsigned, r2);
+// Per-instantiation geometry of a block of MT = 16 CO_TILES output channels.
+template <int CO_TILES>
+struct FxTile {
+  static constexpr int MT = 16 * CO_TILES;
+  static constexpr int CB = MT / 32;                  // weight records per chunk
+  static constexpr int CT2 = CO_TILES / 2;            // output-channel tiles of one wave
+  static constexpr int WPL = MT * 3 * X6_RS;          // elements of one weight piece in LDS: [tap][co][X6_RS] (swizzled rows)
+  static constexpr int WNV = CB * FX_WREC;            // 16-byte vectors of a weight chunk
+  static constexpr int WPT = (WNV + 255) / 256;
+};
+
+// ---- what the plain and the fused kernel share: the weight chunk's way global -> registers -> LDS and the product of one chunk.
+// (The bias preload and the output epilogue stay spelled out in each kernel: moved into a helper, their output-channel index is
+// shared across the main loop and film_cond_fwd_x6_kernel<2> spills 12 instead of 10 registers, profiles/x6_shared_header_ab.txt.)
+// LDS element offset of the thread's i-th weight vector e = tid + 256 i of the chunk's records (chunk invariant)
+template <int CO_TILES>
+__device__ __forceinline__ void fx_weight_plan(int (&wl)[FxTile<CO_TILES>::WPT], int tid) {
+  using G = FxTile<CO_TILES>;
+#pragma unroll
+  for (int i = 0; i < G::WPT; ++i) {
+    const int e = tid + i * 256;
+    const int cb = e / FX_WREC, er = e - cb * FX_WREC;
+    const int row = er >> 2, pc = row / 96, rr = row - pc * 96;            // rr = co * 3 + tap
+    const int co = rr / 3, j = rr - co * 3;
+    wl[i] = pc * G::WPL + x6_swz(j * G::MT + cb * 32 + co, er & 3);
+  }
 }
-// LDS element offset of slot q (8 bf16) of row r. ds_read_b128 serves a wave in four NON-contiguous 16-lane groups ({0-3, 12-15, 20-27}, ...:
-// MI355X_MICROARCH.md, LDS), so a group mixes rows of two k-quarters: padded 80-byte rows made every group 2-way conflicting
-// (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.50 in profiles/r03_pmc.txt). With this XOR any 16 consecutive rows read by lanes
-// (row = base + (lane & 15), q = lane >> 4) touch 16 distinct 4-bank slots in every group, for every base (tools/lds_swizzle_check.py).
-__device__ __forceinline__ int swz(int r, int q) { return r * FX_RS + 8 * (q ^ ((r >> 1) & 3)); }
-__device__ __forceinline__ unsigned pack_hi(unsigned a, unsigned b) {      // {upper half of a, upper half of b}: a in the low 16 bits
-  return __builtin_amdgcn_perm(b, a, 0x07060302u);
+template <int CO_TILES>
+__device__ __forceinline__ void fx_weight_issue(u32x4 (&wr)[FxTile<CO_TILES>::WPT], const srd_t wrs, int c, int tid) {
+  using G = FxTile<CO_TILES>;
+#pragma unroll
+  for (int i = 0; i < G::WPT; ++i)                    // the block's chunk is one linear run of WNV vectors
+    wr[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, (tid + i * 256 < G::WNV) ? (tid + i * 256) * 16 : 0x7f000000,
+                                                                            (blockIdx.y * 5 + c) * (G::WNV * 16), 0));
+}
+template <int CO_TILES>
+__device__ __forceinline__ void fx_weight_commit(unsigned short* ws, const int (&wl)[FxTile<CO_TILES>::WPT], const u32x4 (&wr)[FxTile<CO_TILES>::WPT], int tid) {
+  using G = FxTile<CO_TILES>;
+#pragma unroll
+  for (int i = 0; i < G::WPT; ++i)
+    if (tid + i * 256 < G::WNV) *reinterpret_cast<u32x4*>(ws + wl[i]) = wr[i];
+}
+// One k-block (32 channels) per tap; lane (ln, g): k = 8g .. 8g + 7, wave (wt: step half, wc: output-channel half). Column ln of sub-tile
+// n is step 64 wt + 4 ln + n, which at tap j reads window index 64 wt + 4 ln + (n + j + 3): phase (n + j + 3) & 3, row 16 wt + ln + ((n + j + 3) >> 2)
+template <int CO_TILES>
+__device__ __forceinline__ void fx_product(f32x4 (&acc)[CO_TILES / 2][4], const unsigned short* xt, const unsigned short* ws, int wt, int wc, int ln, int g) {
+  using G = FxTile<CO_TILES>;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    bf16x8 af[G::CT2][3];
+#pragma unroll
+    for (int ct = 0; ct < G::CT2; ++ct)
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) af[ct][pc] = x6_frag(ws + pc * G::WPL, x6_swz(j * G::MT + 16 * (wc * G::CT2 + ct) + ln, g));
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int m = n + j + 3;
+      bf16x8 bf[3];
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) bf[pc] = x6_frag(xt + pc * FX_XPL, x6_swz((m & 3) * FX_PR + 16 * wt + ln + (m >> 2), g));
+#pragma unroll
+      for (int ct = 0; ct < G::CT2; ++ct) x6_mfma(acc[ct][n], af[ct], bf);
+    }
+  }
 }
 
 template <int CO_TILES>
 __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void conv_fwd_x6_kernel(const FwdX6P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
-  constexpr int MT = 16 * CO_TILES;
-  constexpr int CB = MT / 32;                         // weight records per chunk
-  constexpr int CT2 = CO_TILES / 2;                   // output-channel tiles of one wave
-  constexpr int WPL = MT * 3 * FX_RS;                 // elements of one weight piece in LDS: [tap][co][FX_RS] (swizzled rows)
-  constexpr int WNV = CB * FX_WREC;                   // 16-byte vectors of a weight chunk
-  constexpr int WPT = (WNV + 255) / 256;
-  unsigned short* xt = smem16;                        // [3 pieces][4 phases][FX_PR][FX_RS]
-  unsigned short* ws = smem16 + 3 * FX_XPL;           // [3 pieces][3 taps][MT][FX_RS]; both images start on multiples of 8 rows
+  constexpr int MT = FxTile<CO_TILES>::MT, CT2 = FxTile<CO_TILES>::CT2, WPT = FxTile<CO_TILES>::WPT;
+  unsigned short* xt = smem16;
+  unsigned short* ws = smem16 + FX_WS_OFF;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wt = wave & 1, wc = wave >> 1;
@@ -103,14 +148,7 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void conv_fwd_x6_kernel
 
   const int xo = (4 * c4 * T + n0 + 4 * xv) * 4, ho = ((tid & 31) * T + hpos) * 4;      // byte offsets inside a chunk's 32 channel rows
   int wl[WPT];                                        // LDS element offset of the thread's i-th weight vector (chunk invariant)
-#pragma unroll
-  for (int i = 0; i < WPT; ++i) {
-    const int e = tid + i * 256;
-    const int cb = e / FX_WREC, er = e - cb * FX_WREC;
-    const int row = er >> 2, pc = row / 96, rr = row - pc * 96;            // rr = co * 3 + tap
-    const int co = rr / 3, j = rr - co * 3;
-    wl[i] = pc * WPL + swz(j * MT + cb * 32 + co, er & 3);
-  }
+  fx_weight_plan<CO_TILES>(wl, tid);
 
   f32x4 xr[4];
   float hr;
@@ -121,10 +159,7 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void conv_fwd_x6_kernel
     for (int e = 0; e < 4; ++e)
       xr[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (xin && c0 + 4 * c4 + e < p.Cin) ? xo + e * T * 4 : 0x7f000000, c0 * T * 4, 0));
     hr = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (hin && c0 + (tid & 31) < p.Cin) ? ho : 0x7f000000, c0 * T * 4, 0));
-#pragma unroll
-    for (int i = 0; i < WPT; ++i)                     // the block's chunk is one linear run of WNV vectors
-      wr[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, (tid + i * 256 < WNV) ? (tid + i * 256) * 16 : 0x7f000000,
-                                                                              (blockIdx.y * 5 + c) * (WNV * 16), 0));
+    fx_weight_issue<CO_TILES>(wr, wrs, c, tid);
   };
   PROF_DECL
   issue(0);
@@ -139,65 +174,28 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void conv_fwd_x6_kernel
     // 4 (xv + 1) + k: phase k, row xv + 1
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      unsigned hh[4], mm[4], ll[4];
+      f32x4 f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float f0 = xr[e][k];
-        const float f = fmaxf(f0, f0 * p.slope);      // slope in (0, 1]: LeakyReLU; 1: identity
-        split1(f, hh[e], mm[e], ll[e]);
+        f[e] = fmaxf(f0, f0 * p.slope);               // slope in (0, 1]: LeakyReLU; 1: identity
       }
-      const int off = swz(k * FX_PR + xv + 1, c4 >> 1) + 4 * (c4 & 1);
-      *reinterpret_cast<u32x2*>(xt + 0 * FX_XPL + off) = (u32x2){pack_hi(hh[0], hh[1]), pack_hi(hh[2], hh[3])};
-      *reinterpret_cast<u32x2*>(xt + 1 * FX_XPL + off) = (u32x2){pack_hi(mm[0], mm[1]), pack_hi(mm[2], mm[3])};
-      *reinterpret_cast<u32x2*>(xt + 2 * FX_XPL + off) = (u32x2){pack_hi(ll[0], ll[1]), pack_hi(ll[2], ll[3])};
+      x6_split_store4(xt, FX_XPL, x6_swz(k * FX_PR + xv + 1, c4 >> 1) + 4 * (c4 & 1), f);
     }
     if (tid < 64) {                                   // halo: window index 3 (phase 3, row 0) | 132 (phase 0, row 33)
       unsigned h, m, l;
-      split1(fmaxf(hr, hr * p.slope), h, m, l);
-      const int off = swz((tid & 32) ? (FX_PR - 1) : 3 * FX_PR, (tid & 31) >> 3) + (tid & 7);
-      xt[0 * FX_XPL + off] = (unsigned short)(h >> 16);
-      xt[1 * FX_XPL + off] = (unsigned short)(m >> 16);
-      xt[2 * FX_XPL + off] = (unsigned short)(l >> 16);
+      x6_split(fmaxf(hr, hr * p.slope), h, m, l);
+      x6_store3(xt, FX_XPL, x6_swz((tid & 32) ? (FX_PR - 1) : 3 * FX_PR, (tid & 31) >> 3) + (tid & 7), (unsigned short)(h >> 16), (unsigned short)(m >> 16),
+                (unsigned short)(l >> 16));
     }
-#pragma unroll
-    for (int i = 0; i < WPT; ++i)
-      if (tid + i * 256 < WNV) *reinterpret_cast<u32x4*>(ws + wl[i]) = wr[i];
+    fx_weight_commit<CO_TILES>(ws, wl, wr, tid);
     PROF(3)
     __syncthreads();
     PROF(4)
     if (c + 1 < nchunk) issue(c + 1);
     PROF(5)
 
-    // ---- one k-block (32 channels) per tap; lane (ln, g): k = 8g .. 8g + 7. Column ln of sub-tile n is step 64 wt + 4 ln + n, which
-    // at tap j reads window index 64 wt + 4 ln + (n + j + 3): phase (n + j + 3) & 3, row 16 wt + ln + ((n + j + 3) >> 2)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      bf16x8 af[CT2][3];
-#pragma unroll
-      for (int ct = 0; ct < CT2; ++ct)
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-          af[ct][pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ws + pc * WPL + swz(j * MT + 16 * (wc * CT2 + ct) + ln, g)));
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int m = n + j + 3;
-        bf16x8 bf[3];
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-          bf[pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xt + pc * FX_XPL + swz((m & 3) * FX_PR + 16 * wt + ln + (m >> 2), g)));
-#pragma unroll
-        for (int ct = 0; ct < CT2; ++ct) {            // smallest products first
-          f32x4 cc = acc[ct][n];
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][2], bf[0], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[2], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][1], bf[1], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][1], bf[0], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[1], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[0], cc, 0, 0, 0);
-          acc[ct][n] = cc;
-        }
-      }
-    }
+    fx_product<CO_TILES>(acc, xt, ws, wt, wc, ln, g);
     PROF(6)
   }
 
@@ -239,20 +237,14 @@ struct CondX6P {
   int T, Cin, Cout;                     // Cin = nc
   float slope;
 };
-constexpr int FX_ES = 140;               // row stride of the excitation tile: window [n0 - 4, n0 + 132) + 4 (rows 16-byte aligned)
 
 template <int CO_TILES>
 __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void film_cond_fwd_x6_kernel(const CondX6P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
-  constexpr int MT = 16 * CO_TILES;
-  constexpr int CB = MT / 32;
-  constexpr int CT2 = CO_TILES / 2;
-  constexpr int WPL = MT * 3 * FX_RS;
-  constexpr int WNV = CB * FX_WREC;
-  constexpr int WPT = (WNV + 255) / 256;
-  unsigned short* xt = smem16;                        // [3 pieces][4 phases][FX_PR][FX_RS]
-  unsigned short* ws = smem16 + 3 * FX_XPL;           // [3 pieces][3 taps][MT][FX_RS]
-  float* es = reinterpret_cast<float*>(ws + 3 * WPL); // [8][FX_ES] excitation window [n0 - 4, n0 + 132), fp32
+  constexpr int MT = FxTile<CO_TILES>::MT, CT2 = FxTile<CO_TILES>::CT2, WPT = FxTile<CO_TILES>::WPT;
+  unsigned short* xt = smem16;
+  unsigned short* ws = smem16 + FX_WS_OFF;
+  float* es = reinterpret_cast<float*>(smem16 + fx_es_off(MT));              // excitation window [n0 - 4, n0 + 132)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wt = wave & 1, wc = wave >> 1;            // x6 product: step half, output-channel half
@@ -291,14 +283,7 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void film_cond_fwd_x6_k
       bias[ct][r] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f;
     }
   int wl[WPT];
-#pragma unroll
-  for (int i = 0; i < WPT; ++i) {
-    const int e = tid + i * 256;
-    const int cb = e / FX_WREC, er = e - cb * FX_WREC;
-    const int row = er >> 2, pc = row / 96, rr = row - pc * 96;
-    const int co = rr / 3, j = rr - co * 3;
-    wl[i] = pc * WPL + swz(j * MT + cb * 32 + co, er & 3);
-  }
+  fx_weight_plan<CO_TILES>(wl, tid);
 
   __syncthreads();                                    // the excitation tile is in LDS
   // B operand of the cv0 product, chunk invariant: lane (column ln, k-lane g) of k-step s holds E'[k = 4s + g][step], k = ce * 3 + j,
@@ -328,10 +313,7 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void film_cond_fwd_x6_k
     const int c4 = c * 32 + 16 * mt + 4 * g;          // this lane's 4 output channels: 12 contiguous floats of k3
 #pragma unroll
     for (int i = 0; i < 3; ++i) k3v[i] = buf_load4(k3rs, c4 < nc ? (c4 * 3 + 4 * i) * 4 : 0x7f000000);
-#pragma unroll
-    for (int i = 0; i < WPT; ++i)
-      wr[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, (tid + i * 256 < WNV) ? (tid + i * 256) * 16 : 0x7f000000,
-                                                                              (blockIdx.y * 5 + c) * (WNV * 16), 0));
+    fx_weight_issue<CO_TILES>(wr, wrs, c, tid);
   };
   issue(0);
 
@@ -384,66 +366,31 @@ __global__ __launch_bounds__(256, CO_TILES == 2 ? 3 : 2) void film_cond_fwd_x6_k
     // LeakyReLU, zero outside the sequence (cond_var.2's zero padding), split, 8-byte store of the lane's 4 channels per step
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      unsigned hh[4], mm[4], ll[4];
+      f32x4 f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float f0 = own ? v[n][r] : 0.f;
-        split1(fmaxf(f0, f0 * p.slope), hh[r], mm[r], ll[r]);
+        f[r] = fmaxf(f0, f0 * p.slope);
       }
-      const int off = swz(n * FX_PR + 16 * grp + ln + 1, 2 * mt + (g >> 1)) + 4 * (g & 1);
-      *reinterpret_cast<u32x2*>(xt + 0 * FX_XPL + off) = (u32x2){pack_hi(hh[0], hh[1]), pack_hi(hh[2], hh[3])};
-      *reinterpret_cast<u32x2*>(xt + 1 * FX_XPL + off) = (u32x2){pack_hi(mm[0], mm[1]), pack_hi(mm[2], mm[3])};
-      *reinterpret_cast<u32x2*>(xt + 2 * FX_XPL + off) = (u32x2){pack_hi(ll[0], ll[1]), pack_hi(ll[2], ll[3])};
+      x6_split_store4(xt, FX_XPL, x6_swz(n * FX_PR + 16 * grp + ln + 1, 2 * mt + (g >> 1)) + 4 * (g & 1), f);
     }
     if (grp == 0 && ln < 2) {                         // halo steps: window index 3 (phase 3, row 0) | 132 (phase 0, row 33)
       const bool hin = hpos >= 0 && hpos < T;
-      unsigned hh[4], mm[4], ll[4];
+      f32x4 f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float bs = hpos == 0 ? kf[3 * r] : (hpos == T - 1 ? kf[3 * r + 2] : kf[3 * r + 1]);
         const float hv = ch4[r];
         const float f0 = hin ? hv + bs : 0.f;
-        split1(fmaxf(f0, f0 * p.slope), hh[r], mm[r], ll[r]);
+        f[r] = fmaxf(f0, f0 * p.slope);
       }
-      const int off = swz(ln == 1 ? FX_PR - 1 : 3 * FX_PR, 2 * mt + (g >> 1)) + 4 * (g & 1);
-      *reinterpret_cast<u32x2*>(xt + 0 * FX_XPL + off) = (u32x2){pack_hi(hh[0], hh[1]), pack_hi(hh[2], hh[3])};
-      *reinterpret_cast<u32x2*>(xt + 1 * FX_XPL + off) = (u32x2){pack_hi(mm[0], mm[1]), pack_hi(mm[2], mm[3])};
-      *reinterpret_cast<u32x2*>(xt + 2 * FX_XPL + off) = (u32x2){pack_hi(ll[0], ll[1]), pack_hi(ll[2], ll[3])};
+      x6_split_store4(xt, FX_XPL, x6_swz(ln == 1 ? FX_PR - 1 : 3 * FX_PR, 2 * mt + (g >> 1)) + 4 * (g & 1), f);
     }
-#pragma unroll
-    for (int i = 0; i < WPT; ++i)
-      if (tid + i * 256 < WNV) *reinterpret_cast<u32x4*>(ws + wl[i]) = wr[i];
+    fx_weight_commit<CO_TILES>(ws, wl, wr, tid);
     __syncthreads();
     if (c + 1 < nchunk) issue(c + 1);
 
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      bf16x8 af[CT2][3];
-#pragma unroll
-      for (int ct = 0; ct < CT2; ++ct)
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-          af[ct][pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ws + pc * WPL + swz(j * MT + 16 * (wc * CT2 + ct) + ln, g)));
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int m = n + j + 3;
-        bf16x8 bf[3];
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-          bf[pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xt + pc * FX_XPL + swz((m & 3) * FX_PR + 16 * wt + ln + (m >> 2), g)));
-#pragma unroll
-        for (int ct = 0; ct < CT2; ++ct) {
-          f32x4 cc = acc[ct][n];
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][2], bf[0], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[2], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][1], bf[1], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][1], bf[0], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[1], cc, 0, 0, 0);
-          cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ct][0], bf[0], cc, 0, 0, 0);
-          acc[ct][n] = cc;
-        }
-      }
-    }
+    fx_product<CO_TILES>(acc, xt, ws, wt, wc, ln, g);
   }
 
   const int t0 = n0 + 64 * wt + 4 * ln;
@@ -472,10 +419,27 @@ __global__ __launch_bounds__(256) void conv_x6_weight_planes_kernel(const float*
     const int co32 = rest & 31, rec = rest >> 5, cb = rec % cbn, chunk = (rec / cbn) % 5, blk = rec / (cbn * 5);
     const int co = (blk * cbn + cb) * 32 + co32, ci = chunk * 32 + ci32;
     unsigned h = 0, m = 0, l = 0;
-    if (ci < Cin) split1(w[((long)co * Cin + ci) * 3 + j], h, m, l);
-    unsigned short* o = planes + (long)rec * (3 * 32 * 3 * 32) + (co32 * 3 + j) * 32 + ci32;
-    o[0] = (unsigned short)(h >> 16); o[32 * 3 * 32] = (unsigned short)(m >> 16); o[2 * 32 * 3 * 32] = (unsigned short)(l >> 16);
+    if (ci < Cin) x6_split(w[((long)co * Cin + ci) * 3 + j], h, m, l);
+    x6_store3(planes + (long)rec * (3 * 32 * 3 * 32), 32 * 3 * 32, (co32 * 3 + j) * 32 + ci32, (unsigned short)(h >> 16), (unsigned short)(m >> 16),
+              (unsigned short)(l >> 16));
   }
+}
+
+// The geometry both kernels take, and 16-byte alignment of every vector-accessed pointer and batch stride (in floats).
+static bool fx_contract_ok(int Cin, int Cout, int T, int B, std::initializer_list<const void*> ptrs, std::initializer_list<long> strides) {
+  uintptr_t bits = 0;
+  for (const void* q : ptrs) bits |= (uintptr_t)q;
+  long sbits = 0;
+  for (long s : strides) sbits |= s;
+  return Cin > 64 && Cin <= FX_CP && Cout >= 32 && Cout % 32 == 0 && T >= FX_NT && (T & 3) == 0 && (long)Cin * T < (1L << 29) && B > 0 && B < 65536 &&
+         (bits & 15) == 0 && (sbits & 3) == 0;
+}
+
+// One launch of instantiation K (the raised LDS cap and the trace are per instantiation), blocks of MT = x6_mt(Cout) output channels
+template <auto K, int MT, bool EXC, class P>
+static void fx_launch(const P& p, int B, hipStream_t st) {
+  TDVC_BIG_LDS_ONCE(K); TDVC_TRACE(K);
+  hipLaunchKernelGGL(K, dim3((p.T + FX_NT - 1) / FX_NT, p.Cout / MT, B), dim3(256), (size_t)fx_lds_bytes(MT, EXC), st, p);
 }
 
 }  // namespace tdvc
@@ -498,56 +462,33 @@ extern "C" int tdvc_conv_x6_weight_planes(const float* w, int32_t Cout, int32_t 
 extern "C" int tdvc_conv_fwd_x6(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, const void* weight_planes, void* stream) {
   if (!d || !a || !a->x || !a->y || !weight_planes) return tdvc_fail(TDVC_EINVAL, "conv_fwd_x6: null pointer");
   const bool shape = d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->K == 3 && d->dilation == 1 && d->pad == 1 && !d->reflect &&
-                     d->Tin == d->Tout && d->w_cin == 0 && d->Cin > 64 && d->Cin <= FX_CP && d->Cout >= 32 && d->Cout % 32 == 0 && d->Tin >= FX_NT &&
-                     (d->Tin & 3) == 0 && (long)d->Cin * d->Tin < (1L << 29) && d->B > 0 && d->B < 65536;
+                     d->Tin == d->Tout && d->w_cin == 0;
   const bool plain = a->x_xf.kind <= TDVC_XF_LRELU && (a->x_xf.scale == 0.f || a->x_xf.scale == 1.f) && !a->res && !a->add && !a->bias3 && !a->sign_bits &&
                      a->post_act == TDVC_POST_NONE && (a->out_scale == 0.f || a->out_scale == 1.f) &&
                      (a->x_xf.kind == TDVC_XF_NONE || (a->x_xf.slope > 0.f && a->x_xf.slope <= 1.f));
-  const bool al = ((((uintptr_t)a->x) | ((uintptr_t)a->y) | ((uintptr_t)weight_planes)) & 15) == 0 && (a->x_bs & 3) == 0 && (a->y_bs & 3) == 0;
-  if (g_knob[6] || g_force_tile >= 0 || g_force_generic || !shape || !plain || !al) return tdvc_fail(TDVC_EUNSUPPORTED, "conv_fwd_x6: outside the split-bf16 forward kernel's contract");
+  const bool ok = fx_contract_ok(d->Cin, d->Cout, d->Tin, d->B, {a->x, a->y, weight_planes}, {a->x_bs, a->y_bs});
+  if (g_knob[6] || g_force_tile >= 0 || g_force_generic || !shape || !plain || !ok) return tdvc_fail(TDVC_EUNSUPPORTED, "conv_fwd_x6: outside the split-bf16 forward kernel's contract");
   FwdX6P p = {};
   p.x = a->x; p.x_bs = a->x_bs; p.wp = (const unsigned short*)weight_planes; p.bias = a->bias; p.y = a->y; p.y_bs = a->y_bs;
   p.T = d->Tin; p.Cin = d->Cin; p.Cout = d->Cout; p.slope = a->x_xf.kind == TDVC_XF_LRELU ? a->x_xf.slope : 1.f;
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = (d->Tin + FX_NT - 1) / FX_NT;
-  if (x6_mt(d->Cout) == 64) {
-    auto k = conv_fwd_x6_kernel<4>;
-    TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
-    hipLaunchKernelGGL(k, dim3(nt, d->Cout / 64, d->B), dim3(256), (size_t)(3 * FX_XPL + 3 * 64 * 3 * FX_RS) * 2, st, p);
-  } else {
-    auto k = conv_fwd_x6_kernel<2>;
-    TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
-    hipLaunchKernelGGL(k, dim3(nt, d->Cout / 32, d->B), dim3(256), (size_t)(3 * FX_XPL + 3 * 32 * 3 * FX_RS) * 2, st, p);
-  }
+  if (x6_mt(p.Cout) == 64) fx_launch<conv_fwd_x6_kernel<4>, 64, false>(p, d->B, (hipStream_t)stream);
+  else fx_launch<conv_fwd_x6_kernel<2>, 32, false>(p, d->B, (hipStream_t)stream);
   TDVC_CHECK_LAUNCH();
   return TDVC_OK;
 }
 
 extern "C" int tdvc_film_cond_fwd_x6(const tdvc_film_cond_args* a, const void* w2_planes, uint32_t* cv0_sign_bits, int64_t bits_bs, void* stream) {
   if (!a || !a->exc || !a->w0 || !a->k3 || !a->gb || !w2_planes) return tdvc_fail(TDVC_EINVAL, "film_cond_fwd_x6: null pointer");
-  const bool shape = a->n_var == 8 && (a->n_cond & 3) == 0 && a->n_cond > 64 && a->n_cond <= FX_CP && a->C2 >= 32 && a->C2 % 32 == 0 && a->T >= FX_NT &&
-                     (a->T & 3) == 0 && (!cv0_sign_bits || (a->T & 31) == 0) && (long)a->n_cond * a->T < (1L << 29) && a->B > 0 && a->B < 65536 &&
-                     a->slope > 0.f && a->slope <= 1.f;
-  const bool al = ((((uintptr_t)a->exc) | ((uintptr_t)a->gb) | ((uintptr_t)a->cv0) | ((uintptr_t)a->k3) | ((uintptr_t)w2_planes)) & 15) == 0 &&
-                  (a->exc_bs & 3) == 0 && (a->gb_bs & 3) == 0 && (!a->cv0 || (a->cv0_bs & 3) == 0);
-  if (g_knob[6] || g_force_tile >= 0 || g_force_generic || !shape || !al)
+  const bool shape = a->n_var == 8 && (a->n_cond & 3) == 0 && (!cv0_sign_bits || (a->T & 31) == 0) && a->slope > 0.f && a->slope <= 1.f;
+  const bool ok = fx_contract_ok(a->n_cond, a->C2, a->T, a->B, {a->exc, a->gb, a->cv0, a->k3, w2_planes}, {a->exc_bs, a->gb_bs, a->cv0 ? a->cv0_bs : 0});
+  if (g_knob[6] || g_force_tile >= 0 || g_force_generic || !shape || !ok)
     return tdvc_fail(TDVC_EUNSUPPORTED, "film_cond_fwd_x6: outside the fused split-bf16 conditioning forward's contract");
   CondX6P p = {};
   p.exc = a->exc; p.exc_bs = a->exc_bs; p.w0 = a->w0; p.w0_rs = a->n_cond * 3; p.w0_off = (a->n_cond - a->n_var) * 3; p.k3 = a->k3;
   p.wp = (const unsigned short*)w2_planes; p.bias = a->b2; p.cv0 = a->cv0; p.cv0_bs = a->cv0_bs; p.bits = cv0_sign_bits; p.bits_bs = bits_bs;
   p.y = a->gb; p.y_bs = a->gb_bs; p.T = a->T; p.Cin = a->n_cond; p.Cout = a->C2; p.slope = a->slope;
-  hipStream_t st = (hipStream_t)stream;
-  const int nt = (a->T + FX_NT - 1) / FX_NT;
-  const size_t es_bytes = (size_t)8 * FX_ES * sizeof(float);
-  if (x6_mt(a->C2) == 64) {
-    auto k = film_cond_fwd_x6_kernel<4>;
-    TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
-    hipLaunchKernelGGL(k, dim3(nt, a->C2 / 64, a->B), dim3(256), (size_t)(3 * FX_XPL + 3 * 64 * 3 * FX_RS) * 2 + es_bytes, st, p);
-  } else {
-    auto k = film_cond_fwd_x6_kernel<2>;
-    TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
-    hipLaunchKernelGGL(k, dim3(nt, a->C2 / 32, a->B), dim3(256), (size_t)(3 * FX_XPL + 3 * 32 * 3 * FX_RS) * 2 + es_bytes, st, p);
-  }
+  if (x6_mt(p.Cout) == 64) fx_launch<film_cond_fwd_x6_kernel<4>, 64, true>(p, a->B, (hipStream_t)stream);
+  else fx_launch<film_cond_fwd_x6_kernel<2>, 32, true>(p, a->B, (hipStream_t)stream);
   TDVC_CHECK_LAUNCH();
   return TDVC_OK;
 }

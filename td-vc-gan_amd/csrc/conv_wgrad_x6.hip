@@ -1,10 +1,7 @@
 // Weight gradient of a 3-tap stride-1 'same' conv with up to 144 input channels (FiLM's cond_var.2, model/generator.py:86-92:
 // 136 -> 2C, the widest-input layer of the generator and ~10 % of the train step) on the bf16 matrix pipe at fp32 accuracy:
 //     dW[co][ci][j] = sum_{b,t} dy[co][t] * x'[ci][t + j - 1],       x' = LeakyReLU(x) (or x)
-// "Split-bf16 x6": every fp32 operand is cut EXACTLY into three bf16 pieces (x = hi + mid + lo: 3 x 8 significant bits, by
-// truncation, no rounding anywhere) and the product is the six piece products whose weight is >= 2^-16 of the leading one,
-//     a*b ~= lo.hi + hi.lo + mid.mid + mid.hi + hi.mid + hi.hi      (dropped: mid.lo, lo.mid, lo.lo <= 2^-24 relative)
-// each an exact bf16 x bf16 product accumulated in fp32 by v_mfma_f32_16x16x32_bf16. Six 16-cycle instructions do the work of
+// The split-bf16 x6 scheme of split_bf16.h: six 16-cycle v_mfma_f32_16x16x32_bf16 do the work of
 // eight 32-cycle v_mfma_f32_16x16x4_f32: 2.7x the matrix rate of the exact-fp32 path at its accuracy (rel-L2 vs float64
 // 4.5e-7 on the D-layer-5 GEMM shape, profiles/r02_l_split_bf16_probe.txt; the op tests hold 2e-5).
 //
@@ -18,13 +15,9 @@
 // flight during the MFMAs of chunk q; split + LDS store; one k-block of 32 steps = 90 MFMAs per wave.
 #include "launch.h"
 #include "api_util.h"
+#include "split_bf16.h"
 
 namespace tdvc {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct WgX6P {
   const float* dy; long dy_bs;         // [B][R][T]
@@ -36,36 +29,12 @@ struct WgX6P {
 };
 
 constexpr int X6_NT = 32;              // steps per chunk = one k-block
-constexpr int X6_RS = 32;              // bf16 row length: 64 B, no padding; the 16-byte slot q of row r lives at slot q ^ ((r >> 1) & 3) (x6_swz)
 constexpr int X6_XROWS = 144, X6_MT = 32;
-// ds_read_b128 serves a wave in four NON-contiguous 16-lane groups (MI355X_MICROARCH.md, LDS), so a group mixes rows of two k-quarters and
-// the padded 80-byte rows of the first version made every fragment read 2-way conflicting (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.49,
-// profiles/r03_pmc.txt). This XOR is conflict-free for any 16 consecutive rows (tools/lds_swizzle_check.py); planes are multiples of 8 rows.
-__device__ __forceinline__ int x6_swz(int r, int q) { return r * X6_RS + 8 * (q ^ ((r >> 1) & 3)); }
 constexpr int X6_XPL = X6_XROWS * X6_RS;            // elements of one x plane
 constexpr int X6_APL = X6_MT * X6_RS;               // elements of one dy plane of one shift
 constexpr int X6_LDS_BYTES = (3 * X6_XPL + 9 * X6_APL) * 2;
 constexpr int X6_XP = 5;               // float4 per thread of the x tile (144 rows x 8 float4 = 1152 = 4.5 x 256)
 constexpr int X6_NU = 5;               // (row half, channel tile) units per wave: channel tiles (wave >> 1) + 2k
-
-// exact 3-way split of 4 fp32 values into bf16 pieces, packed 4 x 16 bit per piece (element q in bits 16q .. 16q + 15)
-__device__ __forceinline__ void split4(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  unsigned h[4], m[4], l[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float f = v[q];                // (hipcc 7.2: __builtin_bit_cast applied DIRECTLY to a vector element expression reads element 0 for every q)
-    const unsigned u = __builtin_bit_cast(unsigned, f);
-    h[q] = u & 0xffff0000u;
-    const float r1 = f - __builtin_bit_cast(float, h[q]);                  // exact
-    const unsigned u1 = __builtin_bit_cast(unsigned, r1);
-    m[q] = u1 & 0xffff0000u;
-    const float r2 = r1 - __builtin_bit_cast(float, m[q]);                    // exact; <= 8 significant bits left
-    l[q] = __builtin_bit_cast(unsigned, r2) & 0xffff0000u;
-  }
-  hi = (u32x2){(h[0] >> 16) | h[1], (h[2] >> 16) | h[3]};
-  mid = (u32x2){(m[0] >> 16) | m[1], (m[2] >> 16) | m[3]};
-  lo = (u32x2){(l[0] >> 16) | l[1], (l[2] >> 16) | l[3]};
-}
 
 __global__ __launch_bounds__(256, 3) void conv_wgrad_x6_kernel(const WgX6P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned short smem16[];
@@ -127,19 +96,9 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_x6_kernel(const WgX6P p) {
       px3 = av == 0 ? hl : px3;
       const f32x4 sp = {d[1], d[2], d[3], nx0};       // dy[u + 1]
       const f32x4 sm = {px3, d[0], d[1], d[2]};       // dy[u - 1]
-      u32x2 h, m, l;
-      split4(sp, h, m, l);
-      *reinterpret_cast<u32x2*>(as + (0 * 3 + 0) * X6_APL + a_loff) = h;
-      *reinterpret_cast<u32x2*>(as + (0 * 3 + 1) * X6_APL + a_loff) = m;
-      *reinterpret_cast<u32x2*>(as + (0 * 3 + 2) * X6_APL + a_loff) = l;
-      split4(d, h, m, l);
-      *reinterpret_cast<u32x2*>(as + (1 * 3 + 0) * X6_APL + a_loff) = h;
-      *reinterpret_cast<u32x2*>(as + (1 * 3 + 1) * X6_APL + a_loff) = m;
-      *reinterpret_cast<u32x2*>(as + (1 * 3 + 2) * X6_APL + a_loff) = l;
-      split4(sm, h, m, l);
-      *reinterpret_cast<u32x2*>(as + (2 * 3 + 0) * X6_APL + a_loff) = h;
-      *reinterpret_cast<u32x2*>(as + (2 * 3 + 1) * X6_APL + a_loff) = m;
-      *reinterpret_cast<u32x2*>(as + (2 * 3 + 2) * X6_APL + a_loff) = l;
+      x6_split_store4(as + 0 * 3 * X6_APL, X6_APL, a_loff, sp);
+      x6_split_store4(as + 1 * 3 * X6_APL, X6_APL, a_loff, d);
+      x6_split_store4(as + 2 * 3 * X6_APL, X6_APL, a_loff, sm);
     }
     // ---- x tile: LeakyReLU, split, store
 #pragma unroll
@@ -149,12 +108,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_x6_kernel(const WgX6P p) {
         f32x4 v = xv4[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], v[k] * p.x_slope);     // slope in (0, 1]: LeakyReLU; 1: identity
-        u32x2 h, m, l;
-        split4(v, h, m, l);
-        const int off = x6_swz(e >> 3, (e & 7) >> 1) + 4 * (e & 1);
-        *reinterpret_cast<u32x2*>(xs + 0 * X6_XPL + off) = h;
-        *reinterpret_cast<u32x2*>(xs + 1 * X6_XPL + off) = m;
-        *reinterpret_cast<u32x2*>(xs + 2 * X6_XPL + off) = l;
+        x6_split_store4(xs, X6_XPL, x6_swz(e >> 3, (e & 7) >> 1) + 4 * (e & 1), v);
       }
     }
     __syncthreads();
@@ -166,7 +120,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_x6_kernel(const WgX6P p) {
     for (int s = 0; s < 3; ++s)
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc)
-        af[s][pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(as + (s * 3 + pc) * X6_APL + x6_swz(16 * half + ln, g)));
+        af[s][pc] = x6_frag(as + (s * 3 + pc) * X6_APL, x6_swz(16 * half + ln, g));
 #pragma unroll
     for (int k = 0; k < X6_NU; ++k) {
       if (k < nunits) {                               // wave-uniform
@@ -174,18 +128,9 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_x6_kernel(const WgX6P p) {
         bf16x8 bf[3];
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc)
-          bf[pc] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xs + pc * X6_XPL + x6_swz(16 * ct + ln, g)));
+          bf[pc] = x6_frag(xs + pc * X6_XPL, x6_swz(16 * ct + ln, g));
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {                 // tap j pairs x'[u] with dy[u + 1 - j] = shift copy j; smallest products first
-          f32x4 c = acc[k][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][2], bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][0], bf[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][1], bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][1], bf[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][0], bf[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[j][0], bf[0], c, 0, 0, 0);
-          acc[k][j] = c;
-        }
+        for (int j = 0; j < 3; ++j) x6_mfma(acc[k][j], af[j], bf);      // tap j pairs x'[u] with dy[u + 1 - j] = shift copy j
       }
     }
     b = nb; tile = ntile_i;

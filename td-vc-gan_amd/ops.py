@@ -157,6 +157,11 @@ X6_FWD = os.environ.get('TDVC_X6_FWD', '1') == '1'      # split-bf16 x6 forward 
 X6_FWD_MIN_COUT = 32  # smallest Cout routed to the split-bf16 forward (profiles/r03_d_fwd_x6_vs_fp32.txt: 1.19x the fp32 kernel at Cout = 32, 1.5-1.7x above)
 
 
+def _x6_fwd_geometry(k, cin, cout, T):
+    """The shapes both split-bf16 x6 forward kernels take (csrc/conv_fwd_x6.hip: fx_contract_ok). Reads X6_FWD_MIN_COUT at call time."""
+    return k == 3 and 64 < cin <= 160 and cout % 32 == 0 and cout >= X6_FWD_MIN_COUT and T >= 128 and T % 4 == 0
+
+
 def _weight_planes_x6(spec, device):
     """The three exact bf16 pieces of the layer's effective weight ([piece][Cout][tap][160] bf16). Cached on the arena that owns the
     weight and refreshed when it has re-materialised (arena.version: once per forward pass that may follow an optimizer step);
@@ -180,8 +185,8 @@ def conv_fwd_raw(spec: ConvSpec, x, x_xf, post=L.POST_NONE, res=None, add=None, 
     y = out if out is not None else torch.empty((B, spec.cout, d.Tout), dtype=torch.float32, device=x.device)
     _check_layout(x); _check_layout(y)
     bias = (b_ptr if b_ptr is not None else spec.slot.b) or None
-    if (X6_FWD and spec.k == 3 and spec.kind == L.CONV and spec.stride == 1 and spec.dil == 1 and spec.pad == 1 and spec.groups == 1 and not spec.reflect
-            and spec.w_cin == 0 and 64 < spec.cin <= 160 and spec.cout % 32 == 0 and spec.cout >= X6_FWD_MIN_COUT and tin >= 128 and tin % 4 == 0 and post == L.POST_NONE and res is None
+    if (X6_FWD and _x6_fwd_geometry(spec.k, spec.cin, spec.cout, tin) and spec.kind == L.CONV and spec.stride == 1 and spec.dil == 1 and spec.pad == 1
+            and spec.groups == 1 and not spec.reflect and spec.w_cin == 0 and post == L.POST_NONE and res is None
             and add is None and bias3 is None and sign_bits is None and w_ptr is None and x_xf.kind in (L.XF_NONE, L.XF_LRELU) and out_scale == 1.0):
         a = L.ConvFwdArgs(x.data_ptr(), _bs(x), x_xf, spec.slot.w, bias, None, 0, post, SLOPE, 1.0,
                           None, 0, y.data_ptr(), _bs(y), None, None, 0)
@@ -378,7 +383,7 @@ def _film_cond_fwd_x6(ctx, exc, k3, spec_var, spec2):
     shape is outside the kernel's contract (the caller then runs the two launches)."""
     B, nv, T = exc.shape
     nc, C2 = spec2.cin, spec2.cout
-    if not (nv == 8 and nc % 4 == 0 and 64 < nc <= 160 and C2 % 32 == 0 and C2 >= X6_FWD_MIN_COUT and T >= 128 and T % 4 == 0 and spec2.k == 3):
+    if not (nv == 8 and nc % 4 == 0 and _x6_fwd_geometry(spec2.k, nc, C2, T)):
         return None
     if C2 >= 128 and T >= 2048 and not FUSED_COND_FWD_X6_ALWAYS:
         # two or more output-channel blocks per tile each recompute the cv0 tile: at long sequences the two launches are faster

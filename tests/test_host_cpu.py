@@ -104,8 +104,8 @@ def test_mel_filterbank_matches_oracle():
 
 
 def test_x6_lds_swizzle_is_conflict_free_under_b128_lane_groups():
-    """The LDS image of the split-bf16 kernels (conv_fwd_x6.hip `swz`, conv_wgrad_x6.hip `x6_swz`): 64-byte rows, 16-byte slot q of row r
-    stored at slot q ^ ((r >> 1) & 3). Under gfx950's ds_read_b128 lane grouping (four NON-contiguous 16-lane groups, MI355X_MICROARCH.md)
+    """The LDS image of the split-bf16 kernels (`x6_swz` in split_bf16.h, used by conv_fwd_x6.hip and conv_wgrad_x6.hip): 64-byte rows,
+    16-byte slot q of row r stored at slot q ^ ((r >> 1) & 3). Under gfx950's ds_read_b128 lane grouping (four NON-contiguous 16-lane groups, MI355X_MICROARCH.md)
     the MFMA fragment read `row = base + (lane & 15), slot = lane >> 4` must be conflict-free for every base row; the padded 80-byte
     rows the kernels started with are not (measured: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.50, profiles/r03_pmc.txt history)."""
     import importlib.util
