@@ -403,7 +403,41 @@ size_t tdvc_sos_filter_workspace(int32_t B, int32_t T, int32_t n_sections);
 int tdvc_sos_filter(const float* x, int64_t x_bs, const double* sos, int32_t B, int32_t T, int32_t n_sections, int32_t match_rms,
                     float* y, int64_t y_bs, void* workspace, size_t workspace_bytes, void* stream);
 
-int tdvc_contrastive_fwd_bwd(const float* X, const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
+/* Sample-rate conversion and segment preparation of the data pipeline (data/dataset.py:106-150 load_audio): csrc/audio_resample.hip.
+ *
+ * tdvc_resample: resampy's table-interpolated windowed sinc (resampy.resample with its defaults, which is what load_audio calls) as a
+ * polyphase FIR. sr_new / sr_orig = L / M in lowest terms; output t reads from input n = (t*M) div L with phase (t*M) mod L:
+ *     y[b][t] = sum_{j < W} bank[j*bank_tap_stride + (t mod L)*bank_col_stride] * x[b][n - left + 1 + j],
+ * x[b] taken as 0 outside [0, min(n_in[b], T)). bank is float64, W taps by L columns in output order (column q holds the weights
+ * of phase (q*M) mod L; resample.py builds it in numpy float64 from the interpolated filter table and stores it tap-major, strides
+ * (L, 1), which makes a wave's weight loads contiguous). x fp32 [B][T], rows x_bs apart; n_in, n_out int32 [B] on the
+ * device (valid input samples and outputs per row, n_out[b] <= n_out_max); y fp32, rows y_bs >= n_out_max apart. Every element of
+ * y[b][0 .. n_out_max) is written, zeros at and past n_out[b]; x is never read at or past n_in[b]. Accumulated in float64 in a
+ * fixed order and rounded once; no atomics, bit-identical from call to call; one launch, no synchronisation, graph-capturable.
+ * The workspace (tdvc_resample_workspace bytes) receives the float64 sum of squares of the unrounded outputs of every tile of
+ * tdvc_resample_tile() outputs, [B][ceil(n_out_max / tile)], which tdvc_segment takes as tile_sq. TDVC_EUNSUPPORTED for a bank
+ * over 8 MiB (L * W * 8 bytes) or a ratio so small that one tile's input span does not fit the LDS; TDVC_EWORKSPACE for a null or
+ * too small workspace; B == 0 or n_out_max == 0 is a no-op. */
+int32_t tdvc_resample_tile(void);
+size_t tdvc_resample_workspace(int32_t B, int32_t n_out_max);
+int tdvc_resample(const float* x, int64_t x_bs, const int32_t* n_in, const int32_t* n_out, int32_t B, int32_t T, int32_t n_out_max,
+                  const double* bank, int64_t bank_tap_stride, int64_t bank_col_stride, int32_t L, int32_t M, int32_t W,
+                  int32_t left, float* y, int64_t y_bs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* tdvc_segment: the rest of load_audio in one launch. Per row b with n = min(n[b], T) samples of x[b] (fp32, rows x_bs apart):
+ *     gain = 10^(normalization_db / 20) / sqrt(sum(x^2) / n)   (normalize != 0; the sum from tile_sq [B][ntiles] when given, that
+ *            is from tdvc_resample's unrounded outputs, else from x[b] itself; float64, fixed order; 0 when the sum is 0)
+ *     crop  [start[b], start[b] + max_segment) when n > max_segment > 0 (start clamped to [0, n - max_segment]; NULL = 0)
+ *     y[b][s] = x[b][start + s] * gain * aug_gain[b] * sign(aug_sign[b]) inside the crop, 0 behind it, + noise[b][s] * noise_scale
+ * computed in float64 and rounded once. aug_gain, aug_sign, noise (rows noise_bs apart) may be NULL. y is fp32 [B][S] dense and
+ * written completely; gain, when not NULL, receives the float64 normalisation gain per row. max_segment <= S; with
+ * max_segment == 0 (no crop) T <= S. No atomics, no synchronisation, graph-capturable. */
+int tdvc_segment(const float* x, int64_t x_bs, const int32_t* n, int32_t B, int32_t T, const void* tile_sq, int32_t ntiles,
+                 const int32_t* start, const float* aug_gain, const float* aug_sign, const float* noise, int64_t noise_bs,
+                 double noise_scale, int32_t normalize, double normalization_db, int32_t max_segment, int32_t S, float* y,
+                 double* gain, void* stream);
+
+int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 
 const char* tdvc_last_error(void);

@@ -4,7 +4,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     Generator, CollaborativeMultibandDiscriminator, ConditionalInstanceNorm, LatentClassifier,
     losses.{multiscale_spec_loss, multiscale_feat_loss, contrastive_loss}, TrainStep, and the YIN pitch tracker of util/yin.py as
     yin_f0 / track_f0 (pitch.py), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
-    EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py).
+    EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
+    load_audio's resampling and segment preparation as resample / load_segments (resample.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -19,7 +20,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -27,6 +28,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.pitch'), name)
     if name in ('peq_sos', 'sos_filter', 'random_eq', 'corrupt_audio', 'device_batch'):
         return getattr(importlib.import_module(f'{__name__}.corrupt'), name)
+    if name in ('resample_filter', 'resample_bank', 'load_segments'):      # `resample` is the (callable) module itself, above
+        return getattr(importlib.import_module(f'{__name__}.resample'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)
