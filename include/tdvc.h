@@ -114,7 +114,8 @@ int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, void* st
  * stride-1 'same' convs with 65..160 input channels and Cout % 32 == 0 (FiLM cond_var.2), prologue none / LeakyReLU, bias, no
  * other epilogue operand; TDVC_EUNSUPPORTED otherwise (call tdvc_conv_fwd). The weights come pre-split into three exact bf16
  * pieces: tdvc_conv_x6_weight_planes writes tdvc_conv_x6_weight_planes_bytes() bytes from the fp32 weight [Cout][Cin][3]; redo it
- * whenever the weight changes (once per optimizer step). */
+ * whenever the weight changes (once per optimizer step). The image exists for Cout % 32 == 0, 1 <= Cin <= 160, K == 3 only:
+ * otherwise tdvc_conv_x6_weight_planes_bytes returns 0 and tdvc_conv_x6_weight_planes TDVC_EINVAL without writing anything. */
 size_t tdvc_conv_x6_weight_planes_bytes(int32_t Cout, int32_t Cin, int32_t K);
 int tdvc_conv_x6_weight_planes(const float* w, int32_t Cout, int32_t Cin, int32_t K, void* planes, void* stream);
 int tdvc_conv_fwd_x6(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, const void* weight_planes, void* stream);

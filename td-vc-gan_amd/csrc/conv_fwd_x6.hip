@@ -447,7 +447,7 @@ static void fx_launch(const P& p, int B, hipStream_t st) {
 using namespace tdvc;
 
 extern "C" size_t tdvc_conv_x6_weight_planes_bytes(int32_t Cout, int32_t Cin, int32_t K) {
-  if (Cout <= 0 || Cin <= 0 || Cin > FX_CP || K != 3) return 0;
+  if (Cout <= 0 || Cout % 32 != 0 || Cin <= 0 || Cin > FX_CP || K != 3) return 0;      // records hold 32 output channels: no partial image
   return (size_t)3 * Cout * 3 * FX_CP * sizeof(unsigned short);
 }
 
