@@ -13,6 +13,10 @@ instances instead. Two complementary sweeps, both against float64 CPU autograd a
 Each case records which kernel instantiations it launched (tdvc_debug_trace) and asserts the expected one is among them,
 so a silent fall-back to another kernel cannot pass. test_zz_profile_coverage_gpu.py then checks that every tdvc kernel
 instance named in profiles/*kernel_stats.csv was launched by a passing test of this session.
+
+The cases here are contiguous and judged per tensor; test_lean_conv_edges_gpu.py holds the lean kernel's forward and input-grad to the
+element-wise float64 bound at its edge shapes (strided views, guarded outputs, poisoned LDS, every tile, FOLD, reroutes), and
+test_film_block_fwd_edges_gpu.py does the same for the one-launch FiLM block.
 """
 import importlib
 
