@@ -86,6 +86,12 @@ static bool small_group_ok(const tdvc_conv_desc* d) {
   return !g_force_generic && g_knob[2] == 0 && d->kind == TDVC_CONV && d->groups >= 16 && d->Cin == 4 * d->groups && d->Cout == 4 * d->groups &&
          d->dilation == 1 && !d->reflect && d->w_cin == 0 && d->stride >= 2 && d->stride <= 8 && d->K <= 48;
 }
+// Grouped stride-4 conv with 4 -> 16 channels per group (discriminator layers 1-3): forward and input-grad on the MFMA kernels of
+// conv_small_group.hip (group16_*). The weight-grad keeps its route. Same off switches as the small-group route.
+static bool group16_ok(const tdvc_conv_desc* d) {
+  return !g_force_generic && g_knob[2] == 0 && d->kind == TDVC_CONV && d->groups >= 4 && d->Cin == 4 * d->groups && d->Cout == 16 * d->groups &&
+         d->stride == 4 && d->K <= 44 && (d->pad & 3) == 0 && d->dilation == 1 && !d->reflect && d->w_cin == 0;
+}
 static void small_group_base(const tdvc_conv_desc* d, SmallGroupP& q) {
   q.B = d->B; q.G = d->groups; q.Tin = d->Tin; q.Tout = d->Tout; q.K = d->K; q.s = d->stride; q.pad = d->pad;
   q.in_scale = 1.f; q.out_scale = 1.f; q.dy_scale = 1.f;
@@ -110,8 +116,8 @@ static int dispatch_gemm(GemmConvP& p, int B, hipStream_t st) {
   }
 }
 
-// Which kernel a forward or an input-grad call takes, in the order they are tried. The launchers of the first two may decline.
-enum { CV_SMALL_GROUP, CV_LEAN, CV_GENERIC };   // CV_GENERIC: the MFMA or the scalar kernel (use_mfma)
+// Which kernel a forward or an input-grad call takes, in the order they are tried. The launchers of all but the last may decline.
+enum { CV_SMALL_GROUP, CV_GROUP16, CV_LEAN, CV_GENERIC };   // CV_GENERIC: the MFMA or the scalar kernel (use_mfma)
 
 static bool lean_shape_ok(const tdvc_conv_desc* d) {
   return !g_force_generic && d->kind == TDVC_CONV && d->stride == 1 && d->groups == 1 && d->Tin == d->Tout && ((d->Tin & 3) == 0 || d->Tin <= 80);
@@ -135,6 +141,7 @@ static bool lean_fill(const tdvc_conv_desc* d, const tdvc_xform& xf, const long 
 // First route from `from` on that the descriptor and the call's operands can take. CV_LEAN comes with q and xfk filled.
 static int fwd_route(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* a, int from, LeanP& q, int* xfk) {
   if (from <= CV_SMALL_GROUP && small_group_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU && !a->res && !a->add && !a->bias3) return CV_SMALL_GROUP;
+  if (from <= CV_GROUP16 && group16_ok(d) && a->x_xf.kind <= TDVC_XF_LRELU && !a->res && !a->add && !a->bias3) return CV_GROUP16;
   if (from <= CV_LEAN && lean_shape_ok(d) && (d->Cin & 3) == 0) {
     q.x = a->x; q.y = a->y; q.bias = a->bias; q.bias3 = a->bias3; q.res = a->res; q.add = a->add;
     q.w = a->w + (long)d->w_cin_off * d->K; q.Cw = (d->w_cin > 0 ? d->w_cin : d->Cin) * d->K;
@@ -154,13 +161,13 @@ extern "C" int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* 
   int xfk = 0, route = CV_SMALL_GROUP;
   while ((route = fwd_route(d, a, route, q, &xfk)) != CV_GENERIC) {
     hipError_t e;
-    if (route == CV_SMALL_GROUP) {
+    if (route == CV_SMALL_GROUP || route == CV_GROUP16) {
       SmallGroupP g = {};
       small_group_base(d, g);
       g.x = a->x; g.x_bs = a->x_bs; g.w = a->w; g.bias = a->bias; g.y = a->y; g.y_bs = a->y_bs;
       g.act_in = a->x_xf.kind == TDVC_XF_LRELU; g.slope_in = a->x_xf.slope; g.in_scale = scale_or_1(a->x_xf.scale);
       g.post = a->post_act; g.post_slope = a->post_slope; g.out_scale = scale_or_1(a->out_scale);
-      e = launch_small_group_fwd(g, st);
+      e = route == CV_GROUP16 ? launch_group16_fwd(g, st) : launch_small_group_fwd(g, st);
     } else e = launch_conv_lean(q, d->B, xfk, EPI_FWD, st);
     const int rc = launch_rc(e, true);
     if (rc != TRY_NEXT) return rc;
@@ -192,6 +199,8 @@ extern "C" int tdvc_conv_fwd(const tdvc_conv_desc* d, const tdvc_conv_fwd_args* 
 static int dgrad_route(const tdvc_conv_desc* d, const tdvc_conv_dgrad_args* a, int from, LeanP& q, int* xfk) {
   if (from <= CV_SMALL_GROUP && small_group_ok(d) && a->epilogue == TDVC_DG_PLAIN && !a->add &&
       (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))) return CV_SMALL_GROUP;
+  if (from <= CV_GROUP16 && group16_ok(d) && a->epilogue == TDVC_DG_PLAIN && !a->add &&
+      (a->dy_xf.kind == TDVC_XF_NONE || (a->dy_xf.kind == TDVC_XF_MASK_LRELU && a->dy_xf.aux))) return CV_GROUP16;
   if (from <= CV_LEAN && a->wt && lean_shape_ok(d) && (d->Cout & 3) == 0 && (d->K - 1) * d->dilation - d->pad >= 0) {
     q.x = a->dy; q.y = a->dx; q.add = a->add; q.mx = a->x_in; q.gb = a->gb; q.dgb = a->dgb;
     q.Cw = d->Cout * d->K; q.w = a->wt + (long)d->w_cin_off * q.Cw;       // wt rows: [ci] -> (co, k) contiguous
@@ -216,13 +225,13 @@ extern "C" int tdvc_conv_dgrad(const tdvc_conv_desc* d, const tdvc_conv_dgrad_ar
   int xfk = 0, route = CV_SMALL_GROUP;
   while ((route = dgrad_route(d, a, route, q, &xfk)) != CV_GENERIC) {
     hipError_t e;
-    if (route == CV_SMALL_GROUP) {
+    if (route == CV_SMALL_GROUP || route == CV_GROUP16) {
       SmallGroupP g = {};
       small_group_base(d, g);
       g.dy = a->dy; g.dy_bs = a->dy_bs; g.w = a->w; g.y = a->dx; g.y_bs = a->dx_bs;
       g.dy_scale = scale_or_1(a->dy_xf.scale);
       if (a->dy_xf.kind == TDVC_XF_MASK_LRELU) { g.mask = a->dy_xf.aux; g.mask_bs = a->dy_xf.aux_bs; g.m_slope = a->dy_xf.slope; }
-      e = launch_small_group_dgrad(g, st);
+      e = route == CV_GROUP16 ? launch_group16_dgrad(g, st) : launch_small_group_dgrad(g, st);
     } else {
       e = launch_conv_lean(q, d->B, xfk, epi, st);
       if (e == hipErrorNotSupported && q.mbits && a->x_in) {   // shape outside the sign-bit path: the fp32 mask source does the same job

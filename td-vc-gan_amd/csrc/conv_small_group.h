@@ -1,5 +1,5 @@
-// Parameters and launchers of the vector-ALU kernels for grouped strided convs with 4 -> 4 channels per group
-// (conv_small_group.hip). Not part of the C ABI.
+// Parameters and launchers of the kernels for grouped strided convs with 4 input channels per group: 4 -> 4 on the
+// vector ALU, 4 -> 16 (forward / input-grad) on the matrix pipe (conv_small_group.hip). Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,10 +18,14 @@ struct SmallGroupP {
   int post; float post_slope; float in_scale, out_scale, dy_scale; float m_slope;
   int CS;                               // LDS column stride of the time-to-depth tile
   int nsplit;                           // wgrad: sample groups per group of channels
+  int tpr;                              // group16 kernels: consecutive 64-column tiles a wave walks
 };
 
 hipError_t launch_small_group_fwd(SmallGroupP p, hipStream_t st);
 hipError_t launch_small_group_dgrad(SmallGroupP p, hipStream_t st);
+// 4 -> 16 channels per group, stride 4, K <= 44, pad % 4 == 0 on the matrix pipe (x / y / w as above with 16 output channels per group)
+hipError_t launch_group16_fwd(SmallGroupP p, hipStream_t st);
+hipError_t launch_group16_dgrad(SmallGroupP p, hipStream_t st);
 hipError_t launch_small_group_wgrad(SmallGroupP p, float* dw, float* dbias, void* workspace, size_t workspace_bytes, hipStream_t st);
 size_t small_group_wgrad_workspace(int B, int G, int K);
 
