@@ -384,6 +384,32 @@ int tdvc_yin_soft_bwd(const float* x, int64_t x_bs, int32_t B, int32_t T, int32_
                       float threshold, float sample_rate, const float* gy, float* dx, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* Banded max-sum (Viterbi) decoder with a uniform jump floor: the temporal decoding of the reference's inference pitch tracker
+ * (util/crepe.py filtered_pitch(signal, "viterbi"); torchcrepe's decode.viterbi is this programme over a +-12 bin triangular
+ * transition), csrc/pitch_viterbi.hip. Generic in the lattice: the CMDF of tdvc_yin_f0 (scale < 0) or a caller's activations.
+ *   x      lattice fp32 [B][F][n], rows x_bs and frames x_fs >= n elements apart, last axis dense
+ *   obs[f][j] = scale * x[f][j] + prior[j]                       (prior fp32 [n], or NULL for none)
+ *   band   logw fp32 [n][W], lo int32 [n], destination-major: slot k of state j is predecessor i = lo[j] + k; unused slots
+ *          hold -INFINITY
+ *   t(i,j) = max(logw[j][i - lo[j]], -jump) for lo[j] <= i < lo[j] + W, and -jump outside the band; jump = +INFINITY
+ *          disables the floor
+ *   d_0[j] = obs[0][j];  d_f[j] = obs[f][j] + max_i (d_{f-1}[i] + t(i,j)), the LOWEST i among equal maxima; the path ends
+ *          in the lowest j among the maxima of d_{F-1} and is traced back; path int32 [B][F], rows path_bs apart.
+ * fp32 throughout, the maximum of d_f subtracted after every frame (no argmax changes in exact arithmetic, magnitudes stay
+ * bounded for any F). One launch, one block per row; no atomics, no allocation, no synchronisation: graph-capturable, and
+ * bit-identical from call to call. Inputs are finite or -INFINITY; a NaN in the lattice is the caller's error.
+ * The workspace holds the predecessors, uint16 [B][F][n], and for n > 144 one slice per row for a band table that does not fit
+ * the LDS (sized for W = 256, since the query does not take W); the query returns 0 on arguments the decoder refuses.
+ * TDVC_EINVAL for non-positive n, F or W, B < 0, W > n, jump < 0 or NaN, x_fs < n, negative strides, overlapping path rows
+ * and null x, logw, lo or path; TDVC_EUNSUPPORTED for n > 1024 or W > 256; TDVC_EWORKSPACE for a null or too small workspace;
+ * all of them before any launch. B == 0 is a no-op. lo lives on the device, so its entries cannot be refused without a
+ * synchronisation: the kernel clamps each to [0, n - W], which keeps every band inside [0, n) (pitch.viterbi_path checks
+ * a table once on the host). */
+size_t tdvc_viterbi_workspace(int32_t B, int32_t F, int32_t n);
+int tdvc_viterbi_path(const float* x, int64_t x_bs, int64_t x_fs, float scale, const float* prior, const float* logw,
+                      const int32_t* lo, int32_t W, float jump, int32_t B, int32_t F, int32_t n, int32_t* path, int64_t path_bs,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* Random parametric EQ of the data pipeline (util/contentvec/audio_corruption.py random_eq + util.eq_rms_signals, which is all that
  * data/dataset.py:68-86 corrupt_audio returns): csrc/audio_eq.hip.
  *

@@ -3,7 +3,8 @@
 Drop-in surface (same names / signatures / state_dict keys as the reference):
     Generator, CollaborativeMultibandDiscriminator, ConditionalInstanceNorm, LatentClassifier,
     losses.{multiscale_spec_loss, multiscale_feat_loss, contrastive_loss}, TrainStep, and the YIN pitch tracker of util/yin.py as
-    yin_f0 / track_f0 (pitch.py), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
+    yin_f0 / track_f0 (pitch.py; decoder='viterbi' with viterbi_transition / viterbi_path is the temporal decoding of the
+    inference scripts), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
     EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
     load_audio's resampling and segment preparation as resample / load_segments (resample.py).
 
@@ -24,7 +25,7 @@ def __getattr__(name):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
-    if name in ('yin_f0', 'track_f0'):
+    if name in ('yin_f0', 'track_f0', 'viterbi_transition', 'viterbi_path'):
         return getattr(importlib.import_module(f'{__name__}.pitch'), name)
     if name in ('peq_sos', 'sos_filter', 'random_eq', 'corrupt_audio', 'device_batch'):
         return getattr(importlib.import_module(f'{__name__}.corrupt'), name)

@@ -64,7 +64,9 @@ def convert(G, signal, c_tgt, f0_conv, noise=None, start_phase=None):
 @torch.no_grad()
 def convert_audio(G, signal, c_tgt, f0_ratio=1.0, noise=None, start_phase=None, **track_kwargs):
     """Waveform in, waveform out: the F0 track of `signal` [1, 1, T] from `pitch.track_f0` (track_kwargs: hop, sample_rate, pitch_min,
-    pitch_max, threshold), scaled by f0_ratio (the target / source mean-F0 ratio, train.py:636), then `convert`. For the log-F0 mean
-    shift instead, call `track_f0` on both speakers, `shift_f0`, and `convert`."""
+    pitch_max, threshold, decoder, octave_cost, jump_cost), scaled by f0_ratio (the target / source mean-F0 ratio, train.py:636), then
+    `convert`. decoder='viterbi' decodes the track over time, as the reference's inference scripts do (generate_with_target.py:139,
+    util.crepe.filtered_pitch(signal, "viterbi")); the default is the per-frame decision. For the log-F0 mean shift instead, call
+    `track_f0` on both speakers, `shift_f0`, and `convert`."""
     f0_conv = track_f0(signal, **track_kwargs) * f0_ratio
     return convert(G, signal, c_tgt, f0_conv, noise=noise, start_phase=start_phase)

@@ -8,7 +8,17 @@ autocorrelation: same quantity, without the cancellation at its minimum.
 The soft variant is differentiable: with `soft=True`, an input that requires grad and grad mode on, the F0 track carries a
 `grad_fn` whose backward is tdvc_yin_soft_bwd (csrc/pitch_yin_bwd.hip: per-frame gradient, then a gather; no atomics). The hard
 search is piecewise constant and the CMDF of `return_cmdf=True` is a diagnostic output: neither is differentiable.
+
+`decoder='viterbi'` decodes the track over time instead of frame by frame: the counterpart of the reference's inference call
+util.crepe.filtered_pitch(signal, "viterbi") (generate_with_target.py:139), whose torchcrepe decoder is a max-sum dynamic programme
+with a triangular +-240 cent transition. Here the lattice is the CMDF the YIN launch already produces, decoded by
+tdvc_viterbi_path (csrc/pitch_viterbi.hip); `viterbi_transition` builds the band table and `viterbi_path` is the raw decoder for a
+caller with a lattice of its own (CREPE activations included).
 """
+import math
+import weakref
+
+import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -84,26 +94,162 @@ def _yin(x, sample_rate, tau_min, tau_max, stride, threshold, soft, return_cmdf)
     return (f0, cmdf.reshape(*lead, nf, n)) if return_cmdf else f0
 
 
-def yin_f0(signal, sample_rate, pitch_min=20, pitch_max=20000, frame_stride=0.01, threshold=0.1, soft=False, return_cmdf=False):
+DECODERS = (None, 'viterbi')
+THETA = 100.0      # the reference's own sharpness of the CMDF (util/yin.py:132, _softsearch)
+_transition_cache, _dev_transition_cache = {}, {}
+_checked_bands = {}      # id(lo tensor) -> (version, n, W) it was found in range for; the entry goes when the tensor does
+
+
+def _mark_band_checked(lo, n, W):
+    if id(lo) not in _checked_bands:
+        weakref.finalize(lo, _checked_bands.pop, id(lo), None)
+    _checked_bands[id(lo)] = (lo._version, n, W)
+
+
+def _dev_key(device):
+    device = torch.device(device)
+    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+
+
+def _transition_host(tau_min, tau_max, half_width_cents):
+    """(logw float64 [n, W], lo int64 [n]) in numpy; see viterbi_transition."""
+    key = (int(tau_min), int(tau_max), float(half_width_cents))
+    if key not in _transition_cache:
+        n = key[1] - 1 - key[0]
+        if n < 1 or not key[2] > 0:
+            raise ValueError('viterbi_transition: needs tau_max - 1 - tau_min >= 1 states and a positive half width')
+        c = 1200.0 * np.log2(np.arange(n, dtype=np.float64) + key[0] + 1)
+        w = np.maximum(1.0 - np.abs(c[None, :] - c[:, None]) / key[2], 0.0)          # w[j, i], symmetric
+        first = (w > 0).argmax(1)
+        W = int((w > 0).sum(1).max())
+        lo = np.minimum(first, n - W)                                                 # bands at the upper end are shifted down, not cut
+        band = np.take_along_axis(w, lo[:, None] + np.arange(W)[None, :], 1)
+        with np.errstate(divide='ignore'):
+            logw = np.where(band > 0, np.log(band), -np.inf)
+        logw.setflags(write=False); lo.setflags(write=False)
+        _transition_cache[key] = (logw, lo)
+    return _transition_cache[key]
+
+
+def viterbi_transition(tau_min, tau_max, half_width_cents=240.0, device=None):
+    """Band table of the triangular pitch transition on the YIN lag lattice -> (logw [n, W] fp32, lo [n] int32) on `device` (default:
+    the current CUDA/ROCm device), n = tau_max - 1 - tau_min states, state s = lag s + tau_min + 1.
+        c_s = 1200 * log2(s + tau_min + 1);  w(i, j) = max(1 - |c_i - c_j| / half_width_cents, 0);  logw = log(w) where w > 0
+    Slot k of row j is predecessor i = lo[j] + k; slots outside the triangle hold -inf; W is the widest band. The table is symmetric
+    and NOT row-normalised: the lag lattice is not uniform in cents, so normalising rows in the lag domain would favour short or
+    long lags. Built in numpy float64, rounded once, cached per argument tuple and device."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    key = (int(tau_min), int(tau_max), float(half_width_cents), _dev_key(device))
+    if key not in _dev_transition_cache:
+        logw, lo = _transition_host(tau_min, tau_max, half_width_cents)
+        t = (torch.from_numpy(logw.astype(np.float32)).to(device), torch.from_numpy(lo.astype(np.int32)).to(device))
+        _mark_band_checked(t[1], logw.shape[0], logw.shape[1])      # in range by construction
+        _dev_transition_cache[key] = t
+    return _dev_transition_cache[key]
+
+
+def viterbi_path(x, logw, lo, scale=1.0, prior=None, jump=math.inf):
+    """Best path through a lattice x [..., F, n] (device tensor, last axis dense) -> int64 [..., F] state indices: the banded
+    max-sum decoder tdvc_viterbi_path (include/tdvc.h has the recursion and the tie rules: lowest predecessor, lowest final state).
+        obs[f][j] = scale * x[f][j] + prior[j];  transition max(logw[j][i - lo[j]], -jump) inside the band, -jump outside it
+    logw [n, W] fp32 and lo [n] int32 are a band table such as `viterbi_transition` returns; prior [n] or None; jump = inf
+    disables the floor. A lo tensor that did not come from `viterbi_transition` is checked on the host the first time it is seen (one
+    synchronisation; pass the same int32 device tensor again and it is not repeated): a band that leaves [0, n) raises ValueError. One launch; not differentiable."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise L.TdvcError('viterbi_path: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
+    if x.dim() < 2:
+        raise ValueError('viterbi_path: lattice must be [F, n] or [..., F, n]')
+    x = x.detach().float()
+    lead, F, n = x.shape[:-2], x.shape[-2], x.shape[-1]
+    if logw.dim() != 2 or logw.shape[0] != n or lo.shape != (n,):
+        raise ValueError(f'viterbi_path: band table {tuple(logw.shape)} / {tuple(lo.shape)} does not match {n} states')
+    logw = logw.to(device=x.device, dtype=torch.float32).contiguous()
+    lo = lo.to(device=x.device, dtype=torch.int32).contiguous()
+    W = logw.shape[1]
+    if _checked_bands.get(id(lo)) != (lo._version, n, W):
+        if n > 0 and W > 0 and (int(lo.min()) < 0 or int(lo.max()) + W > n):
+            raise ValueError(f'viterbi_path: a band of {W} slots leaves [0, {n})')
+        _mark_band_checked(lo, n, W)
+    if prior is not None:
+        prior = prior.to(device=x.device, dtype=torch.float32).contiguous()
+        if prior.shape != (n,):
+            raise ValueError(f'viterbi_path: prior must be [{n}]')
+    x3 = x.reshape(-1, F, n) if x.dim() != 3 else x          # a view wherever the leading axes share one stride
+    B = x3.shape[0]
+    if (n > 1 and x3.stride(2) != 1) or (F > 1 and x3.stride(1) < n) or (B > 1 and x3.stride(0) < 0):
+        x3 = x3.contiguous()
+    x_bs = x3.stride(0) if B > 1 else F * n
+    x_fs = x3.stride(1) if F > 1 else n
+    lib = L.lib()
+    path = torch.empty(B, F, dtype=torch.int32, device=x.device)
+    nbytes = lib.tdvc_viterbi_workspace(B, F, n)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)      # caching allocator: graph-safe
+    L.check(lib.tdvc_viterbi_path(x3.data_ptr(), x_bs, x_fs, float(scale), prior.data_ptr() if prior is not None else None,
+                                  logw.data_ptr(), lo.data_ptr(), W, float(jump), B, F, n, path.data_ptr(), F, ws.data_ptr(), nbytes,
+                                  torch.cuda.current_stream(x.device).cuda_stream))
+    return path.reshape(*lead, F).long()
+
+
+def _check_decoder(who, decoder, soft):
+    if decoder not in DECODERS:
+        raise ValueError(f'{who}: unknown decoder {decoder!r} (known: {DECODERS})')
+    if decoder is not None and soft:
+        raise ValueError(f"{who}: decoder='viterbi' gives a path, which is not differentiable; it cannot be combined with soft=True")
+
+
+def _viterbi_f0(x, sample_rate, tau_min, tau_max, stride, threshold, octave_cost, jump_cost, return_cmdf):
+    """The hard YIN call with its CMDF, then the decoded lag on the frames the hard track calls voiced."""
+    hard, cmdf = _yin(x, sample_rate, tau_min, tau_max, stride, threshold, False, True)
+    n = cmdf.shape[-1]
+    logw, lo = viterbi_transition(tau_min, tau_max, device=cmdf.device)
+    key = ('prior', tau_min, tau_max, float(octave_cost), _dev_key(cmdf.device))
+    if key not in _dev_transition_cache:
+        lag = np.arange(n, dtype=np.float64) + tau_min + 1
+        _dev_transition_cache[key] = torch.from_numpy((-float(octave_cost) * np.log2(lag / (tau_min + 1))).astype(np.float32)).to(cmdf.device)
+    path = viterbi_path(cmdf, logw, lo, scale=-THETA, prior=_dev_transition_cache[key], jump=float(jump_cost))
+    f0 = torch.where(hard != 0, sample_rate / (path + (tau_min + 1)).to(torch.float32), torch.zeros_like(hard))
+    return (f0, cmdf) if return_cmdf else f0
+
+
+
+def yin_f0(signal, sample_rate, pitch_min=20, pitch_max=20000, frame_stride=0.01, threshold=0.1, soft=False, return_cmdf=False,
+           decoder=None, octave_cost=1.0, jump_cost=16.0):
     """YIN pitch of a signal [T], [B, T] or [..., T] -> [..., n_frames] in Hz, 0 = non-periodic frame (reference: util/yin.py:24-85,
     same arguments). Frames of 2*sample_rate/pitch_min samples every frame_stride seconds; n_frames = (max(T, L) - 1) // stride + 1.
     return_cmdf=True also returns the cumulative-mean-normalised difference [..., n_frames, tau_max - 1 - tau_min].
     soft=True on a signal that requires grad gives a differentiable track (the gradient has the signal's shape); the hard track
-    and the CMDF carry no grad_fn."""
+    and the CMDF carry no grad_fn.
+    decoder='viterbi' replaces the per-frame lag by the best path through the CMDF of the same launch (see `track_f0`)."""
+    _check_decoder('yin_f0', decoder, soft)
     tau_min = int(sample_rate / pitch_max)
     tau_max = int(sample_rate / pitch_min)
     stride = int(frame_stride * sample_rate)
+    if decoder == 'viterbi':
+        return _viterbi_f0(signal, sample_rate, tau_min, tau_max, stride, threshold, octave_cost, jump_cost, return_cmdf)
     return _yin(signal, sample_rate, tau_min, tau_max, stride, threshold, soft, return_cmdf)
 
 
-def track_f0(signal, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, threshold=0.1, soft=False):
+def track_f0(signal, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, threshold=0.1, soft=False, decoder=None, octave_cost=1.0,
+             jump_cost=16.0):
     """signal [B, 1, T] -> F0 track [B, 1, T // hop + 1] in Hz, 0 = unvoiced: the frame count of the reference's CREPE front end
     (pad=True), which is what `infer.convert`, `infer.shift_f0` and `TrainStep` take. YIN yields T // hop frames for an utterance
     of whole hops, so the last frame is repeated once; `f0_to_excitation` drops that frame, as the reference does.
-    soft=True selects the softmax-weighted period, differentiable with respect to a signal that requires grad."""
+    soft=True selects the softmax-weighted period, differentiable with respect to a signal that requires grad.
+    decoder='viterbi' (the reference's inference setting, generate_with_target.py:139) decodes the lag over time: the best path
+    through obs = -100 * CMDF - octave_cost * log2(lag / lag_min) under the triangular +-240 cent transition of
+    `viterbi_transition` with a uniform floor of -jump_cost, so that a pitch reset costs jump_cost instead of being impossible.
+    f0 = sample_rate / lag of the path on the frames the hard tracker calls voiced and 0 elsewhere: voicing decisions are
+    exactly those of decoder=None. octave_cost = 1 and jump_cost = 16 were chosen on synthetic signals (a glide whose fundamental
+    fades against its second harmonic under noise, and the pitch resets of the test fixtures), not on speech; 0.5 .. 1 and
+    10 .. 16 gave the same tracks there. Not differentiable: with soft=True it raises ValueError."""
     if signal.dim() != 3 or signal.shape[1] != 1:
         raise ValueError('track_f0: signal must be [B, 1, T]')
+    _check_decoder('track_f0', decoder, soft)
     T = signal.shape[-1]
-    f0 = _yin(signal[:, 0], sample_rate, int(sample_rate / pitch_max), int(sample_rate / pitch_min), int(hop), threshold, soft, False)
+    tau_min, tau_max = int(sample_rate / pitch_max), int(sample_rate / pitch_min)
+    if decoder == 'viterbi':
+        f0 = _viterbi_f0(signal[:, 0], sample_rate, tau_min, tau_max, int(hop), threshold, octave_cost, jump_cost, False)
+    else:
+        f0 = _yin(signal[:, 0], sample_rate, tau_min, tau_max, int(hop), threshold, soft, False)
     idx = torch.arange(T // int(hop) + 1, device=f0.device).clamp_(max=f0.shape[-1] - 1)
     return f0.index_select(-1, idx).unsqueeze(1)
