@@ -464,6 +464,46 @@ int tdvc_segment(const float* x, int64_t x_bs, const int32_t* n, int32_t B, int3
                  double noise_scale, int32_t normalize, double normalization_db, int32_t max_segment, int32_t S, float* y,
                  double* gain, void* stream);
 
+/* Objective evaluation (test_scripts/common/test_mcd.py): mel-cepstra of a power spectrum and exact dynamic time warping.
+ *
+ * tdvc_sp2mc (csrc/eval_mcep.hip): the mel-cepstrum of order `order` and warping alpha of a power spectrum P[0 .. n_fft/2]:
+ *     c = irfft(log(max(P, floor)));  c[0] /= 2;  mc = freqt(c[0 .. n_fft/2], order, alpha)
+ * where freqt is SPTK's frequency-transform recursion: with b = 1 - alpha^2 and g = 0 at the start, for i = -m1 .. 0 (m1 = n_fft/2)
+ *     d = g;  g[0] = c[-i] + alpha d[0];  g[1] = b d[0] + alpha d[1];  g[j] = d[j-1] + alpha (d[j] - g[j-1]) for j >= 2
+ * and mc = the final g[0 .. order]. This is believed to be what pysptk.sp2mc(P, order, alpha) computes; parity with an installed
+ * pysptk has NOT been checked. Everything after the logarithm is linear, so the caller passes it as mat, float64
+ * [order + 1][nbins] dense (evaluate.sp2mc_matrix builds it on the host by pushing unit vectors through the recursion), and the
+ * device computes mc[b][f][:] = mat . log(max(P[b][f][:], floor)) with the logarithm and the sums in float64, rounded once to fp32.
+ * power is addressed as power[b * p_bs + f * p_fs + k * p_ns] (elements): [B][nbins][F] of this library's STFT and a caller's
+ * [F][nbins] envelope both go in without a copy. mc fp32 [B][F][order + 1] dense. One launch, one block per frame, no atomics, a
+ * fixed summation order, graph-capturable. TDVC_EINVAL for negative B, F or strides, nbins < 2, order outside [0, nbins - 1], a
+ * floor that is not positive and finite, null pointers; TDVC_EUNSUPPORTED for nbins > 2049 or order > 255; B == 0 or F == 0 is a
+ * no-op.
+ *
+ * tdvc_dtw (csrc/eval_dtw.hip): exact DTW of B pairs x[b] fp32 [n[b]][D], y[b] fp32 [m[b]][D] (batch strides x_bs / y_bs, frame
+ * strides x_fs / y_fs >= D, last axis dense). n, m int32 [B] on the DEVICE (NULL = N / M for every pair), clamped to [0, N] /
+ * [0, M]; frames at and past n[b] / m[b] are never read. Local distance d(i, j) in fp32 from direct differences:
+ *     TDVC_DTW_L2 sqrt(sum_d (x - y)^2)   (fastdtw's dist=2)      TDVC_DTW_L1 sum_d |x - y|      TDVC_DTW_SQ sum_d (x - y)^2
+ *     C(0,0) = d(0,0);  C(i,j) = d(i,j) + min(C(i-1,j), C(i,j-1), C(i-1,j-1)),  the FIRST minimum in the order up, left, diagonal
+ *     len(0,0) = 1;     len(i,j) = len(chosen predecessor) + 1
+ * C is carried in float64. cost[b] = C(n-1, m-1) float64, length[b] = len(n-1, m-1) int32 = the number of cells of the optimal
+ * path under that tie rule. path, when not NULL, int32 rows path_bs >= 2 (N + M - 1) apart: (i, j) pairs from (0, 0) to
+ * (n-1, m-1), then -1 up to N + M - 1 pairs. A pair with n[b] == 0 or m[b] == 0 gets cost NaN and length 0 and nothing else is
+ * written for it (its path row included). The tie order is believed to be fastdtw's; that has NOT been checked, and fastdtw is an
+ * approximation (radius 1) whose cost this exact programme bounds from below. One launch, one block per pair; no atomics, no
+ * allocation, no synchronisation: graph-capturable, bit-identical from call to call. The workspace holds one boundary row per pair
+ * (float64 + int32 [B][M]) and, with a path, 2-bit directions [B][N][ceil(M/16)] uint32; the query returns 0 on arguments the
+ * call refuses. TDVC_EINVAL for B < 0, non-positive N, M or D, an unknown metric, frame strides < D, negative strides,
+ * overlapping path rows, null x, y, cost or length; TDVC_EUNSUPPORTED for N or M > 4096 or D > 64; TDVC_EWORKSPACE for a null or
+ * too small workspace; all before any launch. B == 0 is a no-op. */
+enum { TDVC_DTW_L2 = 0, TDVC_DTW_L1 = 1, TDVC_DTW_SQ = 2 };
+int tdvc_sp2mc(const float* power, int64_t p_bs, int64_t p_fs, int64_t p_ns, const double* mat, int32_t B, int32_t F, int32_t nbins,
+               int32_t order, float floor_, float* mc, void* stream);
+size_t tdvc_dtw_workspace(int32_t B, int32_t N, int32_t M, int32_t want_path);
+int tdvc_dtw(const float* x, int64_t x_bs, int64_t x_fs, const float* y, int64_t y_bs, int64_t y_fs, const int32_t* n, const int32_t* m,
+             int32_t B, int32_t N, int32_t M, int32_t D, int32_t metric, double* cost, int32_t* length, int32_t* path, int64_t path_bs,
+             void* workspace, size_t workspace_bytes, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

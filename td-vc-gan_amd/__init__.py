@@ -6,7 +6,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     yin_f0 / track_f0 (pitch.py; decoder='viterbi' with viterbi_transition / viterbi_path is the temporal decoding of the
     inference scripts), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
     EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
-    load_audio's resampling and segment preparation as resample / load_segments (resample.py).
+    load_audio's resampling and segment preparation as resample / load_segments (resample.py), and the objective evaluation of
+    test_scripts/common/test_mcd.py as mcd / dtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats (evaluate.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -21,7 +22,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -31,6 +32,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.corrupt'), name)
     if name in ('resample_filter', 'resample_bank', 'load_segments'):      # `resample` is the (callable) module itself, above
         return getattr(importlib.import_module(f'{__name__}.resample'), name)
+    if name in ('dtw', 'mcd', 'f0_stats', 'sp2mc', 'sp2mc_matrix', 'mel_cepstrum'):
+        return getattr(importlib.import_module(f'{__name__}.evaluate'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

@@ -85,6 +85,7 @@ XF_NONE, XF_LRELU, XF_FILM_LRELU, XF_MASK_LRELU, XF_MASK_TANH = range(5)
 CONV, CONV_TRANSPOSE = 0, 1
 POST_NONE, POST_LRELU, POST_TANH = 0, 1, 2
 DG_PLAIN, DG_MASK_LRELU, DG_FILM = 0, 1, 2
+DTW_L2, DTW_L1, DTW_SQ = 0, 1, 2      # tdvc_dtw metric (include/tdvc.h)
 RESAMPLE_TO = 256      # outputs per block of tdvc_resample (= tdvc_resample_tile(), csrc/audio_resample.hip RS_TO)
 
 # name -> (restype, argtypes); every symbol include/tdvc.h declares
@@ -172,6 +173,10 @@ SIGNATURES = {
                            _vp, C.c_size_t, _vp]),
     'tdvc_segment': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_int32, C.c_double,
                           C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    'tdvc_sp2mc': (_i, [_vp, _i64, _i64, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp]),
+    'tdvc_dtw_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_dtw': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
+                      _vp, C.c_size_t, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

@@ -1,0 +1,307 @@
+"""Objective evaluation on the device: the reference's test_scripts/common/test_mcd.py (mfcc_dist + f0_ratio) as library calls.
+
+    reference                                            here
+    pyworld.dio / stonemask (F0, voicing)                pitch.yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005), or the caller's tracks
+    pyworld.cheaptrick (spectral envelope)               a plain Hann STFT power spectrum (`mel_cepstrum`); a caller with a WORLD
+                                                         envelope passes it to `sp2mc` and gets the reference's call
+    pysptk.sp2mc(sp, 24, 0.42)                           sp2mc: tdvc_sp2mc (csrc/eval_mcep.hip), the definition in include/tdvc.h
+    fastdtw(test, ref, dist=2) -> dist / len(path)       dtw: tdvc_dtw (csrc/eval_dtw.hip), the EXACT programme
+
+Three parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: the envelope is
+not CheapTrick's, `sp2mc` is believed to be pysptk's, and `dtw` is exact where fastdtw is an approximation with radius 1, so the
+cost here is a lower bound on fastdtw's (the tie order up, left, diagonal is believed to be fastdtw's tuple order).
+
+Nothing here synchronises with the host: lengths and voicing stay on the device, the voiced frames are compacted by a prefix
+sum and a scatter, and the per-pair lengths go into the kernel as device int32.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .arena import ConvSlot
+from .ops import ConvSpec, _stream
+
+METRICS = {'l2': L.DTW_L2, 'l1': L.DTW_L1, 'sq': L.DTW_SQ}
+DTW_MAX_LEN, DTW_MAX_D = 4096, 64      # csrc/eval_dtw.hip
+POWER_FLOOR = 1e-10                    # default floor under the logarithm: -100 dB against a full-scale bin of power 1
+
+_matrix_cache, _dev_matrix_cache, _stft_cache = {}, {}, {}
+
+
+def _dev_key(device):
+    device = torch.device(device)
+    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+
+
+def _need_cuda(who, *ts):
+    for t in ts:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.TdvcError(f'{who}: the HIP path needs CUDA/ROCm tensors (there is no CPU fallback)')
+
+
+# ------------------------------------------------------------------------------------------------------------ mel-cepstrum
+def _freqt(c, order, alpha):
+    """SPTK's frequency transform of c [..., m1 + 1] -> [..., order + 1] (float64; the recursion of include/tdvc.h)."""
+    b = 1.0 - alpha * alpha
+    g = np.zeros(c.shape[:-1] + (order + 1,), np.float64)
+    for i in range(c.shape[-1] - 1, -1, -1):
+        d = g.copy()
+        g[..., 0] = c[..., i] + alpha * d[..., 0]
+        if order >= 1:
+            g[..., 1] = b * d[..., 0] + alpha * d[..., 1]
+        for j in range(2, order + 1):
+            g[..., j] = d[..., j - 1] + alpha * (d[..., j] - g[..., j - 1])
+    return g
+
+
+def sp2mc_matrix(n_fft, order=24, alpha=0.42):
+    """float64 [order + 1, n_fft/2 + 1] with mc = matrix @ log(P): the unit vectors of log P pushed through irfft, c[0] / 2 and
+    the frequency-transform recursion. Host numpy, cached per argument tuple (read-only)."""
+    key = (int(n_fft), int(order), float(alpha))
+    if key not in _matrix_cache:
+        n_fft, order, alpha = key
+        if n_fft < 2 or n_fft % 2 or not 0 <= order <= n_fft // 2 or not abs(alpha) < 1:
+            raise ValueError('sp2mc_matrix: needs an even n_fft >= 2, 0 <= order <= n_fft/2 and |alpha| < 1')
+        nb = n_fft // 2 + 1
+        c = np.fft.irfft(np.eye(nb), n=n_fft, axis=1)[:, :nb].copy()      # row k: the cepstrum of the k-th unit vector of log P
+        c[:, 0] *= 0.5
+        m = np.ascontiguousarray(_freqt(c, order, alpha).T)
+        m.setflags(write=False)
+        _matrix_cache[key] = m
+    return _matrix_cache[key]
+
+
+def _matrix_on(device, n_fft, order, alpha):
+    key = (int(n_fft), int(order), float(alpha), _dev_key(device))
+    if key not in _dev_matrix_cache:
+        _dev_matrix_cache[key] = torch.tensor(sp2mc_matrix(n_fft, order, alpha), device=device)
+    return _dev_matrix_cache[key]
+
+
+def sp2mc(power, order=24, alpha=0.42, floor=POWER_FLOOR, layout='fn'):
+    """Mel-cepstrum of a power spectrum (device fp32) -> fp32 [..., n_frames, order + 1]; tdvc_sp2mc, one launch.
+    layout='fn': power is [n_frames, n_bins] or [B, n_frames, n_bins], the layout of a WORLD envelope (pysptk.sp2mc's argument);
+    layout='nf': [B, n_bins, n_frames], the layout of this package's conv STFT. Any strides: nothing is copied. n_bins = n_fft/2 + 1."""
+    _need_cuda('sp2mc', power)
+    if layout not in ('fn', 'nf') or power.dim() not in (2, 3):
+        raise ValueError("sp2mc: power must be [F, N] / [B, F, N] with layout='fn' or [B, N, F] with layout='nf'")
+    p = power.detach()
+    if p.dtype != torch.float32:
+        p = p.float()
+    p3 = p[None] if p.dim() == 2 else p
+    if layout == 'nf':
+        p3 = p3.transpose(1, 2)
+    B, F, nb = p3.shape
+    if min(p3.stride()) < 0:
+        p3 = p3.contiguous()
+    mat = _matrix_on(p.device, 2 * (nb - 1), order, alpha)
+    mc = torch.empty(B, F, order + 1, dtype=torch.float32, device=p.device)
+    L.check(L.lib().tdvc_sp2mc(p3.data_ptr(), p3.stride(0), p3.stride(1), p3.stride(2), mat.data_ptr(), B, F, nb, order, float(floor),
+                               mc.data_ptr(), _stream(p)))
+    return mc[0] if power.dim() == 2 else mc
+
+
+class _Stft:
+    """Periodic-Hann windowed DFT as Conv1d(1 -> 2 Fp, K = n_fft, stride = hop) on the HIP conv kernels (losses.MelSpec's front end
+    with a free hop); Fp = n_fft/2 + 1 padded to a multiple of 4, real parts in channels [0, F), imaginary in [Fp, Fp + F)."""
+
+    def __init__(self, n_fft, hop, device):
+        F = n_fft // 2 + 1
+        self.F, self.Fp, self.n_fft, self.hop = F, (F + 3) // 4 * 4, n_fft, hop
+        n = np.arange(n_fft)
+        win = 0.5 - 0.5 * np.cos(2 * np.pi * n / n_fft)
+        ang = 2 * np.pi * np.outer(np.arange(F), n) / n_fft
+        basis = np.zeros((2 * self.Fp, 1, n_fft), np.float64)
+        basis[:F, 0] = np.cos(ang) * win
+        basis[self.Fp:self.Fp + F, 0] = -np.sin(ang) * win
+        self.basis = torch.from_numpy(basis.astype(np.float32)).to(device)
+        self.spec = ConvSpec(1, 2 * self.Fp, n_fft, stride=hop)
+        self.spec.slot = ConvSlot(self.basis.data_ptr(), 0, 0, 0, trainable=False)
+
+    def power(self, x):
+        """x [B, 1, T] -> |STFT|^2 [B, Fp, 1 + T // hop] (centred frames, reflect padding)."""
+        x = x.contiguous()
+        B, _, T = x.shape
+        pad = self.n_fft // 2
+        lib = L.lib()
+        xp = torch.empty((B, 1, T + 2 * pad), dtype=torch.float32, device=x.device)
+        L.check(lib.tdvc_reflect_pad_fwd(x.data_ptr(), xp.data_ptr(), B, T, pad, _stream(x)))
+        spec = ops.conv_fwd_raw(self.spec, xp, ops._xf())
+        pw = torch.empty((B, self.Fp, spec.shape[2]), dtype=torch.float32, device=x.device)
+        L.check(lib.tdvc_power_fwd(spec.data_ptr(), pw.data_ptr(), B, self.Fp, spec.shape[2], _stream(x)))
+        return pw
+
+
+def mel_cepstrum(signal, sample_rate=16000, n_fft=1024, hop=80, order=24, alpha=0.42, lengths=None, floor=POWER_FLOOR):
+    """signal [B, 1, T] (device fp32) -> mel-cepstra fp32 [B, 1 + T // hop, order + 1]: periodic Hann window of n_fft samples, frame f
+    centred on sample f * hop (reflect padding of n_fft/2, as torch.stft(center=True)), power spectrum through the conv STFT and
+    tdvc_power_fwd, then `sp2mc`. hop is in samples (80 = the reference's 5 ms at 16 kHz); sample_rate is recorded in the
+    signature for symmetry with `mcd` and does not enter the arithmetic. The envelope is a plain STFT, NOT WORLD's CheapTrick.
+    With lengths (device integers [B], valid samples per row) the result is (mc, n_frames) with n_frames = 1 + lengths // hop as
+    device int32; frames whose window reaches past lengths[b] see whatever the row holds there (zero padding, usually)."""
+    _need_cuda('mel_cepstrum', signal)
+    if signal.dim() != 3 or signal.shape[1] != 1:
+        raise ValueError('mel_cepstrum: signal must be [B, 1, T]')
+    if n_fft % 2 or n_fft < 4 or hop < 1 or signal.shape[-1] <= n_fft // 2:
+        raise ValueError('mel_cepstrum: needs an even n_fft, hop >= 1 and more than n_fft/2 samples (reflect padding)')
+    key = (int(n_fft), int(hop), _dev_key(signal.device))
+    if key not in _stft_cache:
+        _stft_cache[key] = _Stft(int(n_fft), int(hop), signal.device)
+    st = _stft_cache[key]
+    pw = st.power(signal.detach().float())
+    mc = sp2mc(pw[:, :st.F], order, alpha, floor, layout='nf')
+    if lengths is None:
+        return mc
+    return mc, (1 + torch.div(lengths.to(signal.device), int(hop), rounding_mode='floor')).clamp(0, mc.shape[1]).to(torch.int32)
+
+
+# ------------------------------------------------------------------------------------------------------------ DTW
+def _len_arg(who, v, B, device):
+    if v is None:
+        return None
+    v = torch.as_tensor(v, device=device) if not torch.is_tensor(v) else v.to(device)
+    if v.shape != (B,):
+        raise ValueError(f'{who}: lengths must be [{B}]')
+    return v.to(torch.int32).contiguous()
+
+
+def _frames3(who, t):
+    if t.dim() not in (2, 3):
+        raise ValueError(f'{who}: sequences must be [N, D] or [B, N, D]')
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    t3 = t[None] if t.dim() == 2 else t
+    B, N, D = t3.shape
+    if (D > 1 and t3.stride(2) != 1) or (N > 1 and t3.stride(1) < D) or (B > 1 and t3.stride(0) < 0):
+        t3 = t3.contiguous()
+    return t3, (t3.stride(0) if B > 1 else N * D), (t3.stride(1) if N > 1 else D)
+
+
+def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
+    """Exact dynamic time warping of x [B, N, D] against y [B, M, D] (device fp32; [N, D] / [M, D] for one pair) ->
+    (cost float64 [B], length int32 [B][, path int64 [B, N + M - 1, 2]]); tdvc_dtw, one launch, no host synchronisation.
+    x_len / y_len: device integers [B], the valid frames of each pair (None = all); frames past them are never read.
+    metric: 'l2' Euclidean norm (fastdtw's dist=2), 'l1', 'sq' squared Euclidean, each in fp32 from direct differences; the
+    accumulated cost is float64. Ties: the first minimum in the order up (i-1, j), left (i, j-1), diagonal. length is the number
+    of cells of that path, so cost / length is the reference's figure. The path starts at (0, 0) and is padded with -1.
+    A pair with a length of 0 gives cost NaN, length 0 and a path of -1. N, M <= 4096 and D <= 64."""
+    _need_cuda('dtw', x, y)
+    if metric not in METRICS:
+        raise ValueError(f'dtw: unknown metric {metric!r} (known: {sorted(METRICS)})')
+    if x.dim() != y.dim():
+        raise ValueError('dtw: x and y must both be [N, D] or both [B, N, D]')
+    single = x.dim() == 2
+    x3, x_bs, x_fs = _frames3('dtw', x)
+    y3, y_bs, y_fs = _frames3('dtw', y)
+    B, N, D = x3.shape
+    if y3.shape[0] != B or y3.shape[2] != D:
+        raise ValueError(f'dtw: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in batch or feature size')
+    M = y3.shape[1]
+    dev = x3.device
+    xl, yl = _len_arg('dtw', x_len, B, dev), _len_arg('dtw', y_len, B, dev)
+    lib = L.lib()
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    P = N + M - 1
+    path = torch.full((B, max(P, 0), 2), -1, dtype=torch.int32, device=dev) if return_path else None
+    nbytes = lib.tdvc_dtw_workspace(B, N, M, int(return_path)) if B > 0 else 0
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)      # caching allocator: graph-safe
+    L.check(lib.tdvc_dtw(x3.data_ptr(), x_bs, x_fs, y3.data_ptr(), y_bs, y_fs, xl.data_ptr() if xl is not None else None,
+                         yl.data_ptr() if yl is not None else None, B, N, M, D, METRICS[metric], cost.data_ptr(), length.data_ptr(),
+                         path.data_ptr() if return_path else None, 2 * P, ws.data_ptr(), nbytes, _stream(x3)))
+    if single:
+        cost, length, path = cost[0], length[0], (path[0] if return_path else None)
+    return (cost, length, path.long()) if return_path else (cost, length)
+
+
+# ------------------------------------------------------------------------------------------------------------ MCD
+def f0_stats(f0_test, f0_ref):
+    """The F0 statistics of test_mcd.py:83-84 and :116 from two tracks [..., F] in Hz (0 = unvoiced; the two may differ in F) ->
+    dict of float64 tensors [...]: over the voiced frames v of each track,
+        diff_f0_mean = mean(log f_test[v]) - mean(log f_ref[v])
+        diff_f0_var  = log(var f_test[v]) - log(var f_ref[v])      (population variance, numpy's default)
+        f0_ratio     = mean f_ref[v] / mean f_test[v]
+    Plain tensor arithmetic in float64 on whichever device holds the tracks; a track without voiced frames gives NaN."""
+    def moments(f):
+        f = f.double()
+        v = f > 0
+        n = v.sum(-1).double()
+        mean = torch.where(v, f, torch.zeros_like(f)).sum(-1) / n
+        mlog = torch.where(v, torch.log(torch.where(v, f, torch.ones_like(f))), torch.zeros_like(f)).sum(-1) / n
+        var = torch.where(v, (f - mean[..., None]) ** 2, torch.zeros_like(f)).sum(-1) / n
+        return mean, mlog, var
+    mt, lt, vt = moments(f0_test)
+    mr, lr, vr = moments(f0_ref)
+    return dict(diff_f0_mean=lt - lr, diff_f0_var=torch.log(vt) - torch.log(vr), f0_ratio=mr / mt)
+
+
+def compact_voiced(mc, voiced):
+    """mc [B, F, D], voiced bool [B, F] -> (the voiced frames of each row moved to its front, in order, [B, F, D]; their count
+    int32 [B]). A prefix sum and a scatter: no host synchronisation. Rows past the count hold NaN."""
+    B, F, D = mc.shape
+    dest = torch.where(voiced, voiced.cumsum(1) - 1, torch.full_like(voiced, F, dtype=torch.int64))      # unvoiced frames go to a spare row
+    out = torch.full((B, F + 1, D), float('nan'), dtype=mc.dtype, device=mc.device)
+    out.scatter_(1, dest[..., None].expand(B, F, D), mc)
+    out[:, F] = float('nan')
+    return out[:, :F], voiced.sum(1).to(torch.int32)
+
+
+def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, mel_kwargs):
+    """Mel-cepstra of the voiced frames of sig [B, 1, T], compacted, their count, and the F0 track used."""
+    B, _, T = sig.shape
+    mc = mel_cepstrum(sig, sample_rate=sample_rate, hop=hop, **mel_kwargs)
+    if f0 is None:
+        from . import pitch
+        f0 = pitch.yin_f0(sig[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
+    elif f0.dim() != 2 or f0.shape[0] != B:
+        raise ValueError(f'{who}: an F0 track must be [B, n_frames]')
+    F = min(mc.shape[1], f0.shape[1])
+    mc, f0 = mc[:, :F], f0[:, :F]
+    if length is None:
+        valid = torch.ones(B, F, dtype=torch.bool, device=sig.device)
+    else:
+        nfr = torch.div(length.to(sig.device) + (hop - 1), hop, rounding_mode='floor')      # frames centred inside the row
+        valid = torch.arange(F, device=sig.device)[None, :] < nfr[:, None]
+    f0 = torch.where(valid, f0, torch.zeros_like(f0))
+    if drop_c0:
+        mc = mc[:, :, 1:]
+    seq, count = compact_voiced(mc, f0 > 0)
+    return seq, count, f0
+
+
+def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None, f0_ref=None, drop_c0=False, db=False, min_voiced=10,
+        **mel_kwargs):
+    """Mel-cepstral distortion of test [B, 1, T1] against ref [B, 1, T2] (device waveforms; *_len: valid samples per row as device
+    integers [B]) -> dict of device tensors [B]: the counterpart of test_mcd.py's mfcc_dist + f0_ratio.
+
+    Mel-cepstra at a 5 ms hop (hop = sample_rate / 200 samples; mel_kwargs go to `mel_cepstrum`: n_fft, order, alpha, floor).
+    Voicing from yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005) or from the caller's f0_test / f0_ref [B, n_frames].
+    Frame alignment: STFT frame f and YIN frame f are both centred on sample f * hop (the STFT reflects n_fft/2 samples, YIN
+    zero-pads half a frame), so frame f of one is frame f of the other; the STFT has one frame more when T is a multiple of
+    hop, and the common frames are kept. With a length, the frames centred inside the row, f * hop < length, count.
+    The voiced frames of each side are compacted on the device and aligned by `dtw` (metric 'l2').
+        mcd = cost / path_len      plain Euclidean distance including c0: the reference's number
+        drop_c0=True leaves c0 out; db=True multiplies by 10 / ln(10) * sqrt(2): together the conventional MCD in dB
+        path_len, n_test, n_ref    cells of the path, voiced frames of each side
+        diff_f0_mean, diff_f0_var, f0_ratio      `f0_stats` of the two tracks
+    Every entry is float64, and every entry is NaN for a pair with fewer than min_voiced voiced frames on either side (the
+    reference returns NaN under 10 on the test side). Nothing synchronises with the host."""
+    _need_cuda('mcd', test, ref)
+    for s in (test, ref):
+        if s.dim() != 3 or s.shape[1] != 1 or s.shape[0] != test.shape[0]:
+            raise ValueError('mcd: waveforms must be [B, 1, T] with one batch size')
+    hop = int(round(sample_rate * 0.005))
+    a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, mel_kwargs)
+    b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, mel_kwargs)
+    if a.shape[1] > DTW_MAX_LEN or b.shape[1] > DTW_MAX_LEN:
+        raise ValueError(f'mcd: more than {DTW_MAX_LEN} frames ({DTW_MAX_LEN * 0.005:.1f} s); evaluate shorter segments')
+    cost, length = dtw(a, b, na, nb, metric='l2')
+    ok = (na >= min_voiced) & (nb >= min_voiced)
+    nan = torch.full_like(cost, float('nan'))
+    scale = 10.0 / math.log(10.0) * math.sqrt(2.0) if db else 1.0
+    out = dict(mcd=scale * cost / length.double(), path_len=length.double(), n_test=na.double(), n_ref=nb.double(), **f0_stats(f0a, f0b))
+    return {k: torch.where(ok, v, nan) for k, v in out.items()}
