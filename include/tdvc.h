@@ -504,6 +504,46 @@ int tdvc_dtw(const float* x, int64_t x_bs, int64_t x_fs, const float* y, int64_t
              int32_t B, int32_t N, int32_t M, int32_t D, int32_t metric, double* cost, int32_t* length, int32_t* path, int64_t path_bs,
              void* workspace, size_t workspace_bytes, void* stream);
 
+/* tdvc_cheaptrick (csrc/eval_cheaptrick.hip): WORLD's CheapTrick spectral envelope (M. Morise, "CheapTrick, a spectral envelope
+ * estimator for high-quality speech synthesis", Speech Communication 67, 2015; WORLD's cheaptrick.cpp / common.cpp), the
+ * pyworld.cheaptrick(signal, f0, time_axis, sr, fft_size=1024) step of the reference's world_analyze, and optionally the
+ * mel-cepstrum of that envelope in the same launch. **Parity with pyworld has NOT been checked** (pyworld is not available to
+ * this repository); what the tests pin is the definition below. N = n_fft, h = N/2, df = fs/N; frame fr of row b is centred on
+ * sample pos = fr * hop (WORLD's matlab_round(t fs + 0.001) at t = fr * 5 ms when hop = fs/200); len = the row's valid length,
+ * lengths[b] clamped to [0, T] (NULL = T); lin(y, p) = y[j] + (y[j+1] - y[j]) (p - j) with j = floor(p) kept inside the array.
+ *   effective F0   f = f0[b][fr] if it is finite and 3 fs/(N - 3) < f0 <= fs/4, else 500 (WORLD's kDefaultF0: an unvoiced frame).
+ *                  The fs/4 cap is this library's: WORLD has none and reads out of range far above it.
+ *   window         half = floor(1.5 fs/f + 0.5) (halves away from zero), k = -half .. half (2 half + 1 <= N - 3);
+ *                  w[k] = 0.5 cos(pi f k/(1.5 fs)) + 0.5, w /= sqrt(sum w^2); s[k] = x[b][clamp(pos + k, 0, len - 1)] w[k]
+ *                  (a row with len = 0 counts as zeros), s -= w sum(s)/sum(w); s is zero-padded to N from offset 0
+ *   power          P[i] = |FFT_N(s)[i]|^2, i = 0 .. h
+ *   DC correction  P[i] += lin(P, (f - i df)/df) for i < 1 + floor(f N/fs), the added values from the uncorrected P
+ *   smoothing      wd = 2 f/3, bd = floor(wd N/fs) + 1, m = [P[bd] .. P[1], P[0] .. P[h], P[h-1] .. P[h-bd]], seg = cumsum(m df),
+ *                  S[i] = (lin(seg, i + wd/(2 df) + bd - 0.5) - lin(seg, i - wd/(2 df) + bd - 0.5)) / wd: the mean over
+ *                  [i df - wd/2, i df + wd/2] of the staircase whose steps are centred on the bins, mirrored at 0 and at Nyquist
+ *   safeguard      S = max(S, floor) + 2.2e-16. WORLD instead adds 1e-12 randn to the windowed samples and 2.2e-16 |randn| to S
+ *                  from its own generator; this is the deterministic counterpart, so frames of digital silence (and any bin under
+ *                  the floor) differ from WORLD's
+ *   lifter         C = Re FFT_N(log S extended evenly to N points); for n = 0 .. h, q = n/fs:
+ *                  c[n] = C[n] sl[n] cl[n] / N, sl[0] = 1, sl[n] = sin(pi f q)/(pi f q), cl[n] = (1 - 2 q1) + 2 q1 cos(2 pi f q)
+ *   envelope       env[i] = exp(Re FFT_N(c extended evenly)[i]), i = 0 .. h
+ *   mel-cepstrum   irfft(log env)[n] is c[n], so tdvc_sp2mc's definition applied to env is freqt(c with c[0] halved) = G . c' with
+ *                  G float64 [order + 1][h + 1] dense, the frequency transform of the unit vectors (evaluate.cheaptrick_mc_matrix):
+ *                  no inverse transform, no exp and no fp32 round trip through the envelope
+ * signal fp32, addressed as signal[b * s_bs + t * s_ts], samples at and past len never read; f0 fp32 at f0[b * f0_bs + fr * f0_fs];
+ * env fp32 [B][F][h + 1] and mc fp32 [B][F][order + 1] dense, either may be NULL but not both, mc needs G. Float64 throughout,
+ * rounded once at the store: the smoothing is a difference of running sums, so a bin 10^(r/10) under the frame's peak carries a
+ * relative error of about 4e-15 * 10^(r/10) in float64 (one rounding of fp32 down to some 70 dB under the peak; in fp32 the
+ * valleys of a 76 dB frame are lost outright). One launch, one block per frame, no atomics, fixed summation orders: bit-identical
+ * from call to call; no allocation, no synchronisation, graph-capturable.
+ * TDVC_EINVAL for negative B, F, T or strides, hop or fs < 1, a floor that is not positive and finite, a q1 that is not finite,
+ * env and mc both NULL, mc without G, order outside [0, h], an fs with 500 Hz outside (3 fs/(N - 3), fs/4], null signal or f0;
+ * TDVC_EUNSUPPORTED for n_fft other than 512, 1024, 2048 and for more than 2^31 - 1 frames; all before any launch.
+ * B == 0 or F == 0 is a no-op. */
+int tdvc_cheaptrick(const float* signal, int64_t s_bs, int64_t s_ts, const int32_t* lengths, int32_t T, const float* f0, int64_t f0_bs,
+                    int64_t f0_fs, int32_t B, int32_t F, int32_t hop, int32_t fs, int32_t n_fft, double q1, double floor_,
+                    const double* G, int32_t order, float* env, float* mc, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

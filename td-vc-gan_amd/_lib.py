@@ -174,6 +174,8 @@ SIGNATURES = {
     'tdvc_segment': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_int32, C.c_double,
                           C.c_int32, C.c_int32, _vp, _vp, _vp]),
     'tdvc_sp2mc': (_i, [_vp, _i64, _i64, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp]),
+    'tdvc_cheaptrick': (_i, [_vp, _i64, _i64, _vp, C.c_int32, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                             C.c_double, _vp, C.c_int32, _vp, _vp, _vp]),
     'tdvc_dtw_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_dtw': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
                       _vp, C.c_size_t, _vp]),

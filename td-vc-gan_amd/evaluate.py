@@ -2,14 +2,18 @@
 
     reference                                            here
     pyworld.dio / stonemask (F0, voicing)                pitch.yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005), or the caller's tracks
-    pyworld.cheaptrick (spectral envelope)               a plain Hann STFT power spectrum (`mel_cepstrum`); a caller with a WORLD
-                                                         envelope passes it to `sp2mc` and gets the reference's call
+    pyworld.cheaptrick (spectral envelope)               cheaptrick: tdvc_cheaptrick (csrc/eval_cheaptrick.hip), the definition in include/tdvc.h;
+                                                         opt-in (envelope='cheaptrick' in `mel_cepstrum` / `mcd`, which then take the mel-cepstrum
+                                                         from the same launch); the default stays a plain Hann STFT power spectrum
     pysptk.sp2mc(sp, 24, 0.42)                           sp2mc: tdvc_sp2mc (csrc/eval_mcep.hip), the definition in include/tdvc.h
     fastdtw(test, ref, dist=2) -> dist / len(path)       dtw: tdvc_dtw (csrc/eval_dtw.hip), the EXACT programme
 
-Three parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: the envelope is
-not CheapTrick's, `sp2mc` is believed to be pysptk's, and `dtw` is exact where fastdtw is an approximation with radius 1, so the
-cost here is a lower bound on fastdtw's (the tie order up, left, diagonal is believed to be fastdtw's tuple order).
+Three parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: **parity of
+`cheaptrick` with pyworld is still unchecked** (it follows WORLD's cheaptrick.cpp as restated in include/tdvc.h, with two stated
+deviations: a deterministic floor, S = max(S, floor) + 2.2e-16, where WORLD adds noise from its own generator, so frames of digital
+silence differ; and an F0 above fs/4 counts as unvoiced, where WORLD has no cap and reads out of range), `sp2mc` is believed to be
+pysptk's, and `dtw` is exact where fastdtw is an approximation with radius 1, so the cost here is a lower bound on fastdtw's (the
+tie order up, left, diagonal is believed to be fastdtw's tuple order).
 
 Nothing here synchronises with the host: lengths and voicing stay on the device, the voiced frames are compacted by a prefix
 sum and a scatter, and the per-pair lengths go into the kernel as device int32.
@@ -27,8 +31,14 @@ from .ops import ConvSpec, _stream
 METRICS = {'l2': L.DTW_L2, 'l1': L.DTW_L1, 'sq': L.DTW_SQ}
 DTW_MAX_LEN, DTW_MAX_D = 4096, 64      # csrc/eval_dtw.hip
 POWER_FLOOR = 1e-10                    # default floor under the logarithm: -100 dB against a full-scale bin of power 1
+# default floor under CheapTrick's smoothed spectrum. Its window has sum w^2 = 1, so white noise of variance v gives P = v per bin: 1e-16
+# is the rounding noise of an fp32 waveform at full scale (2^-48 / 12 = 3e-16), below which nothing in an fp32 signal is information,
+# and it is the size of WORLD's own safeguard (2.2e-16 |randn| added to S), so only frames WORLD would fill with its noise are floored
+CHEAPTRICK_FLOOR = 1e-16
+CHEAPTRICK_N_FFT = (512, 1024, 2048)   # the compiled instances of csrc/eval_cheaptrick.hip
+ENVELOPES = ('stft', 'cheaptrick')
 
-_matrix_cache, _dev_matrix_cache, _stft_cache = {}, {}, {}
+_matrix_cache, _dev_matrix_cache, _stft_cache, _ct_matrix_cache, _ct_dev_matrix_cache = {}, {}, {}, {}, {}
 
 
 def _dev_key(device):
@@ -135,14 +145,101 @@ class _Stft:
         return pw
 
 
-def mel_cepstrum(signal, sample_rate=16000, n_fft=1024, hop=80, order=24, alpha=0.42, lengths=None, floor=POWER_FLOOR):
+def cheaptrick_mc_matrix(n_fft, order=24, alpha=0.42):
+    """float64 [order + 1, n_fft/2 + 1], G = freqt of the unit vectors: the mel-cepstrum of a CheapTrick frame is G @ c' with c' the
+    liftered cepstrum, c[0] halved (include/tdvc.h). Host numpy, cached per argument tuple (read-only)."""
+    key = (int(n_fft), int(order), float(alpha))
+    if key not in _ct_matrix_cache:
+        n_fft, order, alpha = key
+        if n_fft < 2 or n_fft % 2 or not 0 <= order <= n_fft // 2 or not abs(alpha) < 1:
+            raise ValueError('cheaptrick_mc_matrix: needs an even n_fft >= 2, 0 <= order <= n_fft/2 and |alpha| < 1')
+        m = np.ascontiguousarray(_freqt(np.eye(n_fft // 2 + 1), order, alpha).T)
+        m.setflags(write=False)
+        _ct_matrix_cache[key] = m
+    return _ct_matrix_cache[key]
+
+
+def _ct_matrix_on(device, n_fft, order, alpha):
+    key = (int(n_fft), int(order), float(alpha), _dev_key(device))
+    if key not in _ct_dev_matrix_cache:
+        _ct_dev_matrix_cache[key] = torch.tensor(cheaptrick_mc_matrix(n_fft, order, alpha), device=device)
+    return _ct_dev_matrix_cache[key]
+
+
+def _cheaptrick(who, signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, want_env, mc_args):
+    """One tdvc_cheaptrick launch -> (env or None, mc or None); mc_args = (order, alpha) or None."""
+    _need_cuda(who, signal, f0)
+    if signal.dim() != 3 or signal.shape[1] != 1:
+        raise ValueError(f'{who}: signal must be [B, 1, T]')
+    B, _, T = signal.shape
+    if f0.dim() != 2 or f0.shape[0] != B:
+        raise ValueError(f'{who}: an F0 track must be [B, n_frames]')
+    if n_fft not in CHEAPTRICK_N_FFT:
+        raise ValueError(f'{who}: the CheapTrick envelope needs n_fft in {CHEAPTRICK_N_FFT}')
+    hop = int(round(sample_rate / 200)) if hop is None else int(hop)
+    x, f = signal.detach(), f0.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if f.dtype != torch.float32:
+        f = f.float()
+    if min(x.stride()) < 0:
+        x = x.contiguous()
+    if min(f.stride()) < 0:
+        f = f.contiguous()
+    F, nb, dev = f.shape[1], n_fft // 2 + 1, x.device
+    ln = _len_arg(who, lengths, B, dev)
+    env = torch.empty(B, F, nb, dtype=torch.float32, device=dev) if want_env else None
+    mc = mat = None
+    order = 0
+    if mc_args is not None:
+        order, alpha = mc_args
+        mat = _ct_matrix_on(dev, n_fft, order, alpha)
+        mc = torch.empty(B, F, order + 1, dtype=torch.float32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(L.lib().tdvc_cheaptrick(x.data_ptr(), x.stride(0), x.stride(2), ptr(ln), T, f.data_ptr(), f.stride(0), f.stride(1), B, F, hop,
+                                    int(sample_rate), int(n_fft), float(q1), float(floor), ptr(mat), int(order), ptr(env), ptr(mc), _stream(x)))
+    return env, mc
+
+
+def cheaptrick(signal, f0, sample_rate=16000, n_fft=1024, hop=None, q1=-0.15, lengths=None, floor=CHEAPTRICK_FLOOR):
+    """WORLD's CheapTrick spectral envelope of signal [B, 1, T] (device fp32) under the F0 track f0 [B, F] (Hz; 0, NaN, anything at
+    or under 3 fs/(n_fft - 3) or above fs/4 = unvoiced) -> env fp32 [B, F, n_fft/2 + 1], the counterpart of
+    pyworld.cheaptrick(x, f0, t, fs, fft_size=n_fft) with t = 5 ms frames: tdvc_cheaptrick, one launch, the definition in
+    include/tdvc.h. Frame f is centred on sample f * hop, hop = sample_rate / 200 by default (the frame grid of `yin_f0` with
+    frame_stride=0.005). lengths: device integers [B], valid samples per row; samples at and past them are never read (the
+    window repeats the last valid sample, as WORLD does at the end of its input). Any strides: nothing is copied. q1 is the
+    lifter's spectral-recovery weight; floor > 0 replaces WORLD's random safeguard (CHEAPTRICK_FLOOR has the reason).
+    **Parity with pyworld is unchecked.** n_fft is 512, 1024 or 2048."""
+    return _cheaptrick('cheaptrick', signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, True, None)[0]
+
+
+def mel_cepstrum(signal, sample_rate=16000, n_fft=1024, hop=80, order=24, alpha=0.42, lengths=None, floor=None, envelope='stft', f0=None,
+                 q1=-0.15):
     """signal [B, 1, T] (device fp32) -> mel-cepstra fp32 [B, 1 + T // hop, order + 1]: periodic Hann window of n_fft samples, frame f
     centred on sample f * hop (reflect padding of n_fft/2, as torch.stft(center=True)), power spectrum through the conv STFT and
     tdvc_power_fwd, then `sp2mc`. hop is in samples (80 = the reference's 5 ms at 16 kHz); sample_rate is recorded in the
-    signature for symmetry with `mcd` and does not enter the arithmetic. The envelope is a plain STFT, NOT WORLD's CheapTrick.
+    signature for symmetry with `mcd` and does not enter the arithmetic. floor defaults to POWER_FLOOR.
     With lengths (device integers [B], valid samples per row) the result is (mc, n_frames) with n_frames = 1 + lengths // hop as
-    device int32; frames whose window reaches past lengths[b] see whatever the row holds there (zero padding, usually)."""
+    device int32; frames whose window reaches past lengths[b] see whatever the row holds there (zero padding, usually).
+    envelope='cheaptrick': the mel-cepstra of WORLD's CheapTrick envelope instead (`cheaptrick`, whose launch also yields them:
+    no envelope is stored), fp32 [B, F, order + 1] on the frames of the F0 track f0 [B, F]; f0=None runs
+    yin_f0(pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate), as `mcd` does. sample_rate enters the arithmetic, floor
+    defaults to CHEAPTRICK_FLOOR, n_fft is 512, 1024 or 2048, and samples at and past lengths[b] are never read."""
     _need_cuda('mel_cepstrum', signal)
+    if envelope not in ENVELOPES:
+        raise ValueError(f'mel_cepstrum: unknown envelope {envelope!r} (known: {ENVELOPES})')
+    if envelope == 'cheaptrick':
+        if signal.dim() != 3 or signal.shape[1] != 1:
+            raise ValueError('mel_cepstrum: signal must be [B, 1, T]')
+        if f0 is None:
+            from . import pitch
+            f0 = pitch.yin_f0(signal.detach().float()[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
+        mc = _cheaptrick('mel_cepstrum', signal, f0, sample_rate, n_fft, hop, q1, lengths, CHEAPTRICK_FLOOR if floor is None else floor,
+                         False, (order, alpha))[1]
+        if lengths is None:
+            return mc
+        return mc, (1 + torch.div(lengths.to(signal.device), int(hop), rounding_mode='floor')).clamp(0, mc.shape[1]).to(torch.int32)
+    floor = POWER_FLOOR if floor is None else floor
     if signal.dim() != 3 or signal.shape[1] != 1:
         raise ValueError('mel_cepstrum: signal must be [B, 1, T]')
     if n_fft % 2 or n_fft < 4 or hop < 1 or signal.shape[-1] <= n_fft // 2:
@@ -250,15 +347,20 @@ def compact_voiced(mc, voiced):
     return out[:, :F], voiced.sum(1).to(torch.int32)
 
 
-def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, mel_kwargs):
+def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, mel_kwargs):
     """Mel-cepstra of the voiced frames of sig [B, 1, T], compacted, their count, and the F0 track used."""
     B, _, T = sig.shape
-    mc = mel_cepstrum(sig, sample_rate=sample_rate, hop=hop, **mel_kwargs)
+    cheap = envelope == 'cheaptrick'
+    if not cheap:
+        mc = mel_cepstrum(sig, sample_rate=sample_rate, hop=hop, **mel_kwargs)
     if f0 is None:
         from . import pitch
         f0 = pitch.yin_f0(sig[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
     elif f0.dim() != 2 or f0.shape[0] != B:
         raise ValueError(f'{who}: an F0 track must be [B, n_frames]')
+    if cheap:                                                                     # one F0 track for the envelope and for the voicing
+        mc = mel_cepstrum(sig, sample_rate=sample_rate, hop=hop, envelope='cheaptrick', f0=f0, lengths=length, **mel_kwargs)
+        mc = mc[0] if length is not None else mc
     F = min(mc.shape[1], f0.shape[1])
     mc, f0 = mc[:, :F], f0[:, :F]
     if length is None:
@@ -274,11 +376,14 @@ def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, mel_kwargs)
 
 
 def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None, f0_ref=None, drop_c0=False, db=False, min_voiced=10,
-        **mel_kwargs):
+        envelope='stft', **mel_kwargs):
     """Mel-cepstral distortion of test [B, 1, T1] against ref [B, 1, T2] (device waveforms; *_len: valid samples per row as device
     integers [B]) -> dict of device tensors [B]: the counterpart of test_mcd.py's mfcc_dist + f0_ratio.
 
-    Mel-cepstra at a 5 ms hop (hop = sample_rate / 200 samples; mel_kwargs go to `mel_cepstrum`: n_fft, order, alpha, floor).
+    Mel-cepstra at a 5 ms hop (hop = sample_rate / 200 samples; mel_kwargs go to `mel_cepstrum`: n_fft, order, alpha, floor, q1).
+    envelope='stft' (the default) takes them from a plain Hann STFT; envelope='cheaptrick' from WORLD's CheapTrick envelope, as the
+    reference does: the F0 track is obtained first and serves both the envelope and the voicing, frame f of the cepstra IS frame f
+    of the track, and samples at and past a length are never read.
     Voicing from yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005) or from the caller's f0_test / f0_ref [B, n_frames].
     Frame alignment: STFT frame f and YIN frame f are both centred on sample f * hop (the STFT reflects n_fft/2 samples, YIN
     zero-pads half a frame), so frame f of one is frame f of the other; the STFT has one frame more when T is a multiple of
@@ -294,9 +399,11 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
     for s in (test, ref):
         if s.dim() != 3 or s.shape[1] != 1 or s.shape[0] != test.shape[0]:
             raise ValueError('mcd: waveforms must be [B, 1, T] with one batch size')
+    if envelope not in ENVELOPES:
+        raise ValueError(f'mcd: unknown envelope {envelope!r} (known: {ENVELOPES})')
     hop = int(round(sample_rate * 0.005))
-    a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, mel_kwargs)
-    b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, mel_kwargs)
+    a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, envelope, mel_kwargs)
+    b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, envelope, mel_kwargs)
     if a.shape[1] > DTW_MAX_LEN or b.shape[1] > DTW_MAX_LEN:
         raise ValueError(f'mcd: more than {DTW_MAX_LEN} frames ({DTW_MAX_LEN * 0.005:.1f} s); evaluate shorter segments')
     cost, length = dtw(a, b, na, nb, metric='l2')
