@@ -158,6 +158,20 @@ size_t tdvc_debug_trace_dump(char* buf, size_t cap);
 int tdvc_debug_poison_lds(uint32_t word, void* stream);
 /* TOOLS-ONLY: an empty dispatch (pmc_marker_kernel) that separates table entries in a rocprofv3 trace (tools/microbench_kernels.py) */
 int tdvc_debug_marker(void* stream);
+/* TEST-ONLY: one slab fold through the kernel every weight-grad ends with, launched at once (the deferral switch is ignored):
+ *   dst[map(i)] += slab[0][i] + slab[1][i] + ... + slab[nslab-1][i]  for i < n, slab q at slab + q * stride (stride >= n).
+ * Elements i < n_w go to dw, compact rows of `rowlen` mapped onto rows of `dst_row_stride` floats (equal: no mapping); elements
+ * i >= n_w go to dbias[i - n_w] (n_w < 0: no bias part). Slabs are scratch: a fold of more than 8 slabs may leave partial sums
+ * in them. ref = 1 runs the one-load-per-slab reference loop on its own grid instead of the production kernel; the two agree
+ * bit for bit. */
+int tdvc_debug_slab_fold(const float* slab, int32_t nslab, int64_t stride, int64_t n, float* dw, int32_t rowlen, int64_t dst_row_stride,
+                         int64_t n_w, float* dbias, int32_t ref, void* stream);
+/* TOOLS-ONLY: tdvc_debug_fold_log(1) clears and starts, (2) the same with every fold on the reference loop and its grid plan
+ * (the "before" column of tools/fold_traffic.py; switch only with no fold queued), (0) stops a log with one row per fold flush outside graph capture:
+ * {folds, launches, blocks, bytes moved, microseconds between two events around the launches} (the flush then waits for the
+ * stream). tdvc_debug_fold_log_read copies up to cap_rows rows of 5 doubles and returns the number recorded. */
+void tdvc_debug_fold_log(int on);
+size_t tdvc_debug_fold_log_read(double* rows, size_t cap_rows);
 
 /* Fused forward of one FiLM residual block (model/generator.py:96-111), narrow long-sequence case (C == 16, T % 4 == 0, T >= 512,
  * reflect padding (K-1)*dilation/2, 16-byte aligned operands; TDVC_EUNSUPPORTED otherwise -> run the two tdvc_conv_fwd calls):

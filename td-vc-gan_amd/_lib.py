@@ -119,6 +119,9 @@ SIGNATURES = {
     'tdvc_fold_reset': (None, [C.c_void_p]),
     'tdvc_debug_poison_lds': (_i, [C.c_uint32, C.c_void_p]),
     'tdvc_debug_marker': (_i, [C.c_void_p]),
+    'tdvc_debug_slab_fold': (_i, [_vp, C.c_int32, _i64, _i64, _vp, C.c_int32, _i64, _i64, _vp, C.c_int32, _vp]),
+    'tdvc_debug_fold_log': (None, [_i]),
+    'tdvc_debug_fold_log_read': (C.c_size_t, [C.POINTER(C.c_double), C.c_size_t]),
     'tdvc_debug_trace': (None, [_i]),
     'tdvc_debug_trace_dump': (C.c_size_t, [C.c_char_p, C.c_size_t]),
     'tdvc_weight_norm_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

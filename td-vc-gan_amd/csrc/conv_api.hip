@@ -444,3 +444,13 @@ extern "C" int tdvc_film_cond_fwd(const tdvc_film_cond_args* a, void* stream) {
 extern "C" void tdvc_fold_defer(int on) { tdvc::fold_set_defer(on); }
 extern "C" void tdvc_fold_reset(void* stream) { tdvc::fold_reset((hipStream_t)stream); }
 extern "C" int tdvc_fold_flush(void* stream) { return launch_rc(tdvc::fold_flush((hipStream_t)stream)); }
+// Test and tool access to the fold kernel (include/tdvc.h)
+extern "C" int tdvc_debug_slab_fold(const float* slab, int32_t nslab, int64_t stride, int64_t n, float* dw, int32_t rowlen, int64_t dst_row_stride,
+                                    int64_t n_w, float* dbias, int32_t ref, void* stream) {
+  if (n_w < 0) n_w = n;
+  if (!slab || !dw || nslab < 1 || n < 1 || stride < n || n_w > n || rowlen < 1 || dst_row_stride < rowlen || (n_w < n && !dbias))
+    return tdvc_fail(TDVC_EINVAL, "debug_slab_fold: bad arguments");
+  return launch_rc(tdvc::debug_slab_fold(slab, nslab, stride, n, dw, rowlen, dst_row_stride, n_w, dbias, ref, (hipStream_t)stream));
+}
+extern "C" void tdvc_debug_fold_log(int on) { tdvc::fold_log_set(on); }
+extern "C" size_t tdvc_debug_fold_log_read(double* rows, size_t cap_rows) { return tdvc::fold_log_read(rows, cap_rows); }

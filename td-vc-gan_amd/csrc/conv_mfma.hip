@@ -771,8 +771,84 @@ struct FoldBatch { FoldDesc d[FOLD_MAX]; int count, nblocks, partial; };
 // dw[map(i)] += sum_s slab[s][i]; map: compact row-major [rows][rowlen] -> dst row stride (channel-window weights), identity
 // otherwise. grid.y splits the slabs of a fold so small weights still fill the chip, without atomics: with `partial` set, only
 // split folds run and each y-block leaves its sum in its own first slab; the second launch (run_fold_batch) sums those gy
-// partials in y order. Every element is summed in a fixed order: the same bits every run.
+// partials in y order. Every element is summed in a fixed order (0 + slab s0 + slab s0+1 + ...): the same bits every run.
+//
+// The kernel streams nslab x n floats once and is HBM-bound, so it is built around bytes in flight: a thread owns groups of
+// four consecutive elements, loads them as one float4 per slab (fold_vec: slab rows 16-byte aligned) and issues the loads of
+// up to 8 slabs before the first add. The adds stay one chain per element in slab order, so the sums are those of the
+// one-load-per-slab loop (slab_reduce_ref_kernel). gx counts blocks of 256 groups.
+__device__ __forceinline__ bool fold_vec(const FoldDesc& f) { return (f.stride & 3) == 0 && (((uintptr_t)f.slab) & 15) == 0; }
+
+__device__ __forceinline__ float* fold_dst(const FoldDesc& f, long i) {
+  if (i >= f.n_w) return f.dbias + (i - f.n_w);
+  long dst = i;
+  if (f.dst_row_stride != f.rowlen) { const long r = i / f.rowlen; dst = r * f.dst_row_stride + (i - r * f.rowlen); }
+  return f.dw + dst;
+}
+
+// V = 4: float4 loads of whole groups; V = 1: one element per group (unaligned slabs, and the n % 4 tail of aligned ones)
+template <int V>
+__device__ __forceinline__ void fold_groups(const FoldDesc& f, const int partial, const int s0, const int s1, const long i0, const long i1,
+                                            const long first, const long step) {
+  typedef float vec_t __attribute__((ext_vector_type(V)));
+  for (long i = i0 + first * V; i + V <= i1; i += step * V) {
+    const float* src = f.slab + i;
+    vec_t s;
+#pragma unroll
+    for (int e = 0; e < V; ++e) s[e] = 0.f;
+    int q = s0;
+    for (; q + 8 <= s1; q += 8) {
+      vec_t v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const vec_t*>(src + (long)(q + u) * f.stride);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    if (q < s1) {
+      vec_t v[7];
+#pragma unroll
+      for (int u = 0; u < 7; ++u)
+        if (q + u < s1) v[u] = *reinterpret_cast<const vec_t*>(src + (long)(q + u) * f.stride);
+#pragma unroll
+      for (int u = 0; u < 7; ++u)
+        if (q + u < s1) s += v[u];
+    }
+    if (partial) { *reinterpret_cast<vec_t*>(const_cast<float*>(src) + (long)s0 * f.stride) = s; continue; }
+    float* d0 = fold_dst(f, i);
+    // one 16-byte read-modify-write where the group's four destinations are consecutive and aligned: a group never straddles
+    // the weight / bias boundary or a destination row when n_w and rowlen are multiples of 4 (i is one)
+    const bool wide = V == 4 && (f.n_w & 3) == 0 && (i >= f.n_w || f.dst_row_stride == f.rowlen || (f.rowlen & 3) == 0) && (((uintptr_t)d0) & 15) == 0;
+    if (wide) {
+      vec_t* dp = reinterpret_cast<vec_t*>(d0);
+      *dp = *dp + s;
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) *fold_dst(f, i + e) += s[e];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const FoldBatch fb) {
+  int k = 0;
+  for (int i = 1; i < fb.count; ++i)
+    if ((int)blockIdx.x >= fb.d[i].blk0) k = i;
+  const FoldDesc& f = fb.d[k];
+  if (fb.partial && f.gy == 1) return;
+  const int lb = blockIdx.x - f.blk0, bx = lb % f.gx, by = lb / f.gx;
+  const int s0 = by * f.per_y, s1 = min(f.nslab, s0 + f.per_y);
+  const long first = (long)bx * 256 + threadIdx.x, step = (long)f.gx * 256;
+  if (fold_vec(f)) {
+    const long n4 = f.n & ~3L;
+    fold_groups<4>(f, fb.partial, s0, s1, 0, n4, first, step);
+    fold_groups<1>(f, fb.partial, s0, s1, n4, f.n, first, step);
+  } else {
+    fold_groups<1>(f, fb.partial, s0, s1, 0, f.n, first, step);
+  }
+}
+
+// TEST-ONLY reference (tdvc_debug_slab_fold with ref = 1): the one-load-per-slab loop the kernel above replaced, one
+// element per thread and pass. Same order of additions per element; tests require equal bits.
+__global__ __launch_bounds__(256) void slab_reduce_ref_kernel(const FoldBatch fb) {
   int k = 0;
   for (int i = 1; i < fb.count; ++i)
     if ((int)blockIdx.x >= fb.d[i].blk0) k = i;
@@ -784,14 +860,7 @@ __global__ __launch_bounds__(256) void slab_reduce_multi_kernel(const FoldBatch 
     float s = 0.f;
     for (int q = s0; q < s1; ++q) s += f.slab[(long)q * f.stride + i];
     if (fb.partial) { const_cast<float*>(f.slab)[(long)s0 * f.stride + i] = s; continue; }
-    float* dstp;
-    if (i >= f.n_w) dstp = f.dbias + (i - f.n_w);
-    else {
-      long dst = i;
-      if (f.dst_row_stride != f.rowlen) { const long r = i / f.rowlen; dst = r * f.dst_row_stride + (i - r * f.rowlen); }
-      dstp = f.dw + dst;
-    }
-    *dstp += s;
+    *fold_dst(f, i) += s;
   }
 }
 
@@ -842,6 +911,7 @@ __global__ __launch_bounds__(256) void weight_repack_kernel(const GemmConvP p, f
 // ================================================================================================
 // host-side launchers (called from conv_api.cpp)
 #include <map>
+#include <vector>
 namespace tdvc {
 
 // Scratch for the repacked weights of ONE launch, per stream: repack -> conv -> next repack are ordered by the stream, so
@@ -1070,15 +1140,63 @@ static int g_fold_defer = 0;
 static std::mutex g_fold_mu;
 static std::map<hipStream_t, FoldBatch>& fold_pending() { static std::map<hipStream_t, FoldBatch> m; return m; }
 
+// TOOLS-ONLY (tdvc_debug_fold_log, tools/fold_traffic.py): per flush, the bytes its descriptors move and the time of its one or
+// two launches between two events. Off by default; never records during a graph capture (event timing is not capturable).
+struct FoldLogRow { double folds, launches, blocks, bytes, us; };
+static int g_fold_log = 0;
+static std::vector<FoldLogRow>& fold_log_rows() { static std::vector<FoldLogRow> v; return v; }
+struct FoldLogScope {
+  hipEvent_t e0 = nullptr, e1 = nullptr; hipStream_t st; FoldLogRow row;
+  FoldLogScope(const FoldBatch& fb, hipStream_t s) : st(s) {
+    if (!g_fold_log) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return; }
+    double bytes = 0; bool split = false;
+    for (int i = 0; i < fb.count; ++i) {
+      const FoldDesc& f = fb.d[i];
+      // slabs read once; a split fold writes and re-reads gy partials; the gradient is read and written
+      bytes += 4.0 * (double)f.n * ((double)f.nslab + (f.gy > 1 ? 2.0 * f.gy : 0.0) + 2.0);
+      split = split || f.gy > 1;
+    }
+    row = {(double)fb.count, split ? 2.0 : 1.0, (double)fb.nblocks, bytes, 0.0};
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { (void)hipGetLastError(); e0 = nullptr; return; }
+    (void)hipEventRecord(e0, st);
+  }
+  ~FoldLogScope() {
+    if (!e0) return;
+    float ms = 0.f;
+    (void)hipEventRecord(e1, st);
+    if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) { row.us = ms * 1e3; fold_log_rows().push_back(row); }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  }
+};
+void fold_log_set(int on) {      // 2: as 1, and every fold runs slab_reduce_ref_kernel on its own plan (the "before" of an A/B);
+  std::lock_guard<std::mutex> lk(g_fold_mu);      // switch only with no fold queued
+  g_fold_log = (on == 1 || on == 2) ? on : 0;
+  if (g_fold_log) fold_log_rows().clear();
+}
+size_t fold_log_read(double* rows, size_t cap_rows) {
+  std::lock_guard<std::mutex> lk(g_fold_mu);
+  const std::vector<FoldLogRow>& v = fold_log_rows();
+  for (size_t i = 0; i < v.size() && i < cap_rows; ++i) {
+    const double r[5] = {v[i].folds, v[i].launches, v[i].blocks, v[i].bytes, v[i].us};
+    for (int j = 0; j < 5; ++j) rows[i * 5 + j] = r[j];
+  }
+  return v.size();
+}
+
 // Runs the folds of `fb` (consumed): split folds first leave one partial per y-block (in place, in the y-block's first slab),
 // then every fold sums its slabs -- or, when split, its gy partials -- in order.
-static hipError_t run_fold_batch(FoldBatch& fb, hipStream_t st) {
+static hipError_t run_fold_batch(FoldBatch& fb, hipStream_t st, bool ref = false) {
+  ref = ref || g_fold_log == 2;
   bool split = false;
   for (int i = 0; i < fb.count; ++i) split = split || fb.d[i].gy > 1;
-  TDVC_TRACE(slab_reduce_multi_kernel);
+  auto kern = ref ? slab_reduce_ref_kernel : slab_reduce_multi_kernel;
+  if (!ref) TDVC_TRACE(slab_reduce_multi_kernel);
+  FoldLogScope log(fb, st);
   if (split) {
     fb.partial = 1;
-    hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(fb.nblocks), dim3(256), 0, st, fb);
+    hipLaunchKernelGGL(kern, dim3(fb.nblocks), dim3(256), 0, st, fb);
     int nb = 0;
     for (int i = 0; i < fb.count; ++i) {
       FoldDesc& f = fb.d[i];
@@ -1088,7 +1206,7 @@ static hipError_t run_fold_batch(FoldBatch& fb, hipStream_t st) {
     fb.nblocks = nb;
   }
   fb.partial = 0;
-  hipLaunchKernelGGL(slab_reduce_multi_kernel, dim3(fb.nblocks), dim3(256), 0, st, fb);
+  hipLaunchKernelGGL(kern, dim3(fb.nblocks), dim3(256), 0, st, fb);
   fb.count = 0; fb.nblocks = 0;
   return hipGetLastError();
 }
@@ -1108,14 +1226,28 @@ void fold_reset(hipStream_t st) {
   if (it != fold_pending().end()) { it->second.count = 0; it->second.nblocks = 0; }
 }
 
+// Grid plan of one fold. gy / per_y fix the order of additions of a split fold and are planned on the element count as they
+// always were; gx only spreads the groups of the kernel (float4 groups where fold_vec holds) over blocks.
+static void fold_plan(FoldDesc& f, bool ref) {
+  int gx0 = (int)((f.n + 255) / 256); if (gx0 > 2048) gx0 = 2048; if (gx0 < 1) gx0 = 1;
+  int gy = 1;
+  if (f.nslab > 8) { gy = 1024 / gx0; if (gy > (f.nslab + 7) / 8) gy = (f.nslab + 7) / 8; if (gy < 1) gy = 1; }
+  f.per_y = (f.nslab + gy - 1) / gy;
+  f.gy = (f.nslab + f.per_y - 1) / f.per_y;
+  if (ref) { f.gx = gx0; return; }      // the reference kernel's own grid: one element per thread and pass
+  const bool vec = (f.stride & 3) == 0 && (((uintptr_t)f.slab) & 15) == 0;
+  const long groups = vec ? (f.n + 3) / 4 : f.n;
+  long gx = (groups + 255) / 256; if (gx > 8192) gx = 8192; if (gx < 1) gx = 1;
+  f.gx = (int)gx;
+}
+
 hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride,
                               hipStream_t st, long n_w, float* dbias) {
   if (n_w < 0) n_w = n;
-  int gx = (int)((n + 255) / 256); if (gx > 2048) gx = 2048; if (gx < 1) gx = 1;
-  int gy = 1;
-  if (nslab > 8) { gy = 1024 / gx; if (gy > (nslab + 7) / 8) gy = (nslab + 7) / 8; if (gy < 1) gy = 1; }
-  const int per_y = (nslab + gy - 1) / gy;
-  gy = (nslab + per_y - 1) / per_y;
+  FoldDesc d = {};
+  d.slab = slab; d.dw = dw; d.dbias = dbias; d.stride = stride; d.n = n; d.dst_row_stride = dst_row_stride; d.n_w = n_w;
+  d.nslab = nslab; d.rowlen = rowlen;
+  fold_plan(d, g_fold_log == 2);
   if (g_fold_defer) {
     std::lock_guard<std::mutex> lk(g_fold_mu);
     FoldBatch& fb = fold_pending()[st];
@@ -1123,18 +1255,30 @@ hipError_t launch_slab_reduce(const float* slab, int nslab, long stride, long n,
     for (int i = 0; i < fb.count && !clash; ++i)
       clash = fb.d[i].dw == dw || (dbias && fb.d[i].dbias == dbias);
     if (clash) { const hipError_t e = fold_flush_locked(st); if (e != hipSuccess) return e; }
-    FoldDesc& f = fb.d[fb.count++];
-    f.slab = slab; f.dw = dw; f.dbias = dbias; f.stride = stride; f.n = n; f.dst_row_stride = dst_row_stride; f.n_w = n_w;
-    f.nslab = nslab; f.rowlen = rowlen; f.gx = gx; f.gy = gy; f.per_y = per_y; f.blk0 = fb.nblocks;
-    fb.nblocks += gx * gy;
+    d.blk0 = fb.nblocks;
+    fb.d[fb.count++] = d;
+    fb.nblocks += d.gx * d.gy;
     return hipSuccess;
   }
   FoldBatch one = {};
-  FoldDesc& f = one.d[0];
-  f.slab = slab; f.dw = dw; f.dbias = dbias; f.stride = stride; f.n = n; f.dst_row_stride = dst_row_stride; f.n_w = n_w;
-  f.nslab = nslab; f.rowlen = rowlen; f.gx = gx; f.gy = gy; f.per_y = per_y; f.blk0 = 0;
-  one.count = 1; one.nblocks = gx * gy;
+  d.blk0 = 0;
+  one.d[0] = d;
+  one.count = 1; one.nblocks = d.gx * d.gy;
   return run_fold_batch(one, st);
+}
+
+// TEST-ONLY (tdvc_debug_slab_fold): one fold, launched at once whatever the deferral switch says; ref = 1 runs the
+// one-load-per-slab reference kernel on its own grid plan.
+hipError_t debug_slab_fold(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride, long n_w,
+                           float* dbias, int ref, hipStream_t st) {
+  FoldDesc d = {};
+  d.slab = slab; d.dw = dw; d.dbias = dbias; d.stride = stride; d.n = n; d.dst_row_stride = dst_row_stride; d.n_w = n_w < 0 ? n : n_w;
+  d.nslab = nslab; d.rowlen = rowlen;
+  fold_plan(d, ref != 0);
+  FoldBatch one = {};
+  one.d[0] = d;
+  one.count = 1; one.nblocks = d.gx * d.gy;
+  return run_fold_batch(one, st, ref != 0);
 }
 
 hipError_t launch_bias_grad(const Opnd& a, int N, int Ctot, int B, float* dbias, hipStream_t st) {

@@ -19,6 +19,10 @@ hipError_t launch_bias_grad(const Opnd& a, int N, int Ctot, int B, float* dbias,
 hipError_t fold_flush(hipStream_t st);
 void fold_set_defer(int on);
 void fold_reset(hipStream_t st);
+hipError_t debug_slab_fold(const float* slab, int nslab, long stride, long n, float* dw, int rowlen, long dst_row_stride, long n_w,
+                           float* dbias, int ref, hipStream_t st);
+void fold_log_set(int on);
+size_t fold_log_read(double* rows, size_t cap_rows);
 
 // conv_wgrad_lean.hip
 void wgrad_lean_plan(int R, int Cin, int N, int K, int B, int* ntiles, int* tpb, int* ngroups);
