@@ -9,8 +9,10 @@ what this module computes: `peq_sos` (tdvc_peq_sos, the reference's params2sos i
 """
 import math
 
+import numpy as np
 import torch
 
+from . import _host as H
 from . import _lib as L
 from .infer import shift_f0
 from .pitch import track_f0
@@ -22,42 +24,24 @@ N_BANDS = 10
 FC = tuple(math.exp(math.log(60.0) + (math.log(7600.0) - math.log(60.0)) * k / (N_BANDS - 1)) for k in range(N_BANDS))
 F0_HOP = 64
 
-_fc_cache = {}
-
-
-def _default_fc(device):
-    """The reference's ten log-spaced centres 60 .. 7600 Hz as a float64 device tensor, uploaded once per device (so that a later
-    call copies nothing from the host and can be captured into a graph)."""
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    if key not in _fc_cache:
-        _fc_cache[key] = torch.tensor(FC, dtype=torch.float64).to(device)
-    return _fc_cache[key]
-
-
-def _need_device(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.TdvcError(f'{what}: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
-
-
 def peq_sos(gains_db, q, sample_rate=16000, fc=None):
     """Second-order sections of a parametric EQ: gains_db, q [B, n] (dB, Q factor) -> float64 [B, n, 6] on the device, rows
     b0 b1 b2 1 a1 a2. Band 0 is a low shelf, band n-1 a high shelf, the others peaking filters (the reference's params2sos).
     fc: n centre frequencies in Hz, default the reference's ten log-spaced centres."""
-    _need_device(gains_db, 'peq_sos')
+    H.need_device('peq_sos', gains_db)
     dev = gains_db.device
     g = gains_db.detach().to(torch.float32).contiguous()
     qq = q.detach().to(device=dev, dtype=torch.float32).contiguous()
     if g.dim() != 2 or qq.shape != g.shape:
         raise ValueError('peq_sos: gains_db and q must both be [B, n_bands]')
     B, n = g.shape
-    fc_t = _default_fc(dev) if fc is None else torch.as_tensor(fc, dtype=torch.float64).to(dev).contiguous()
+    fc_t = H.device_table(dev, 'peq centres', lambda: np.array(FC)) if fc is None else torch.as_tensor(fc, dtype=torch.float64).to(dev).contiguous()
     if fc_t.shape != (n,):
         raise ValueError(f'peq_sos: {n} bands need {n} centre frequencies, got {tuple(fc_t.shape)}')
     if n < 2:
         raise ValueError('peq_sos: needs at least two bands (a low and a high shelf)')
     sos = torch.empty(B, n, 6, dtype=torch.float64, device=dev)
-    L.check(L.lib().tdvc_peq_sos(g.data_ptr(), qq.data_ptr(), fc_t.data_ptr(), n, float(sample_rate), B, sos.data_ptr(),
-                                 torch.cuda.current_stream(dev).cuda_stream))
+    L.check(L.lib().tdvc_peq_sos(g.data_ptr(), qq.data_ptr(), fc_t.data_ptr(), n, float(sample_rate), B, sos.data_ptr(), H.stream(sos)))
     return sos
 
 
@@ -66,19 +50,9 @@ def sos_filter(signal, sos, match_rms=False):
     one cascade per row, zero initial state) -> the same shape: scipy.signal.sosfilt per row, computed in float64 and rounded once.
     match_rms=True scales each row to the RMS of its input row (util.eq_rms_signals) before that rounding. Rows may be strided;
     only a signal whose last axis is not dense is copied."""
-    _need_device(signal, 'sos_filter')
-    _need_device(sos, 'sos_filter')
-    if signal.dim() not in (1, 2, 3) or (signal.dim() == 3 and signal.shape[1] != 1):
-        raise ValueError('sos_filter: signal must be [T], [B, T] or [B, 1, T]')
-    x = signal.detach().float()
-    shape, T = x.shape, x.shape[-1]
-    x2 = x[:, 0] if x.dim() == 3 else x.reshape(1, T) if x.dim() == 1 else x
-    if T > 1 and x2.stride(-1) != 1:
-        x2 = x2.contiguous()
-    B = x2.shape[0]
-    x_bs = x2.stride(0) if B > 1 else T
-    if x_bs < 0:
-        x2, x_bs = x2.contiguous(), T
+    H.need_device('sos_filter', signal, sos)
+    x2, x_bs, lead = H.rows2('sos_filter', signal)
+    B, T = x2.shape
     sos = sos.detach().to(torch.float64).contiguous()
     if sos.dim() == 2:
         sos = sos.unsqueeze(0)
@@ -86,22 +60,19 @@ def sos_filter(signal, sos, match_rms=False):
         raise ValueError(f'sos_filter: sos must be [B = {B}, n_sections, 6], got {tuple(sos.shape)}')
     S = sos.shape[1]
     lib = L.lib()
-    y = torch.empty(B, T, dtype=torch.float32, device=x.device)      # the kernel writes every element
+    y = torch.empty(B, T, dtype=torch.float32, device=x2.device)      # the kernel writes every element
     nbytes = lib.tdvc_sos_filter_workspace(B, T, S)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    rc = lib.tdvc_sos_filter(x2.data_ptr(), x_bs, sos.data_ptr(), B, T, S, int(bool(match_rms)), y.data_ptr(), T,
-                             ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(x.device).cuda_stream)
-    if rc == L.EUNSUPPORTED:
-        raise ValueError(f'sos_filter: {lib.tdvc_last_error().decode()}')
-    L.check(rc)
-    return y.reshape(shape)
+    ws = H.scratch(nbytes, x2.device)
+    H.check('sos_filter', lib.tdvc_sos_filter(x2.data_ptr(), x_bs, sos.data_ptr(), B, T, S, int(bool(match_rms)), y.data_ptr(), T,
+                                              ws.data_ptr(), nbytes, H.stream(x2)))
+    return y.reshape(lead + (T,))
 
 
 def random_eq(signal, sample_rate=16000, gains_db=None, z=None, generator=None, match_rms=True):
     """Random parametric EQ of signal [T], [B, T] or [B, 1, T] (reference: audio_corruption.random_eq, per row): ten bands at the
     log-spaced centres, gains G ~ U(-12, 12) dB, Q = 2 * 2.5^z with z ~ U(0, 1). The draws are optional inputs, gains_db and z
     [B, 10]; by default they are drawn on the device with `generator`. No host synchronisation anywhere in the call."""
-    _need_device(signal, 'random_eq')
+    H.need_device('random_eq', signal)
     dev = signal.device
     B = 1 if signal.dim() == 1 else signal.shape[0]
     if gains_db is None:
@@ -142,7 +113,7 @@ def device_batch(signal_real, label_src, num_spk, conversion=True, generator=Non
     reads: signal_real, signal_corrupted, label_src, label_tgt, c_src, c_tgt, c_f0_src, c_f0_conv, f0_conv, perm.
     Every random draw is an optional input (gains_db, z [B, 10]; perm [B]; noise_* = (voiced, unvoiced) normal tensors [B, 1, T];
     start_phase_* 1-element tensors), drawn on the device with `generator` otherwise. T must be a multiple of the F0 hop (64)."""
-    _need_device(signal_real, 'device_batch')
+    H.need_device('device_batch', signal_real)
     if signal_real.dim() != 3 or signal_real.shape[1] != 1:
         raise ValueError('device_batch: signal_real must be [B, 1, T]')
     B, _, T = signal_real.shape

@@ -23,10 +23,11 @@ import math
 import numpy as np
 import torch
 
+from . import _host as H
 from . import _lib as L
 from . import ops
 from .arena import ConvSlot
-from .ops import ConvSpec, _stream
+from .ops import ConvSpec
 
 METRICS = {'l2': L.DTW_L2, 'l1': L.DTW_L1, 'sq': L.DTW_SQ}
 DTW_MAX_LEN, DTW_MAX_D = 4096, 64      # csrc/eval_dtw.hip
@@ -38,18 +39,13 @@ CHEAPTRICK_FLOOR = 1e-16
 CHEAPTRICK_N_FFT = (512, 1024, 2048)   # the compiled instances of csrc/eval_cheaptrick.hip
 ENVELOPES = ('stft', 'cheaptrick')
 
-_matrix_cache, _dev_matrix_cache, _stft_cache, _ct_matrix_cache, _ct_dev_matrix_cache = {}, {}, {}, {}, {}
+_stft_cache = {}
 
 
-def _dev_key(device):
-    device = torch.device(device)
-    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
-
-
-def _need_cuda(who, *ts):
-    for t in ts:
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise L.TdvcError(f'{who}: the HIP path needs CUDA/ROCm tensors (there is no CPU fallback)')
+def _signal3(who, signal):
+    H.need_device(who, signal)
+    if signal.dim() != 3 or signal.shape[1] != 1:
+        raise ValueError(f'{who}: signal must be [B, 1, T]')
 
 
 # ------------------------------------------------------------------------------------------------------------ mel-cepstrum
@@ -67,50 +63,46 @@ def _freqt(c, order, alpha):
     return g
 
 
+def _mc_table(who, n_fft, order, alpha):
+    """(key, build) of `who`'s matrix for _host.host_table / device_table: freqt of the unit vectors, for sp2mc_matrix after irfft and c[0] / 2."""
+    n_fft, order, alpha = int(n_fft), int(order), float(alpha)
+    if n_fft < 2 or n_fft % 2 or not 0 <= order <= n_fft // 2 or not abs(alpha) < 1:
+        raise ValueError(f'{who}: needs an even n_fft >= 2, 0 <= order <= n_fft/2 and |alpha| < 1')
+
+    def build():
+        nb = n_fft // 2 + 1
+        c = np.eye(nb)
+        if who == 'sp2mc_matrix':
+            c = np.fft.irfft(c, n=n_fft, axis=1)[:, :nb].copy()      # row k: the cepstrum of the k-th unit vector of log P
+            c[:, 0] *= 0.5
+        m = np.ascontiguousarray(_freqt(c, order, alpha).T)
+        m.setflags(write=False)
+        return m
+    return (who, n_fft, order, alpha), build
+
+
 def sp2mc_matrix(n_fft, order=24, alpha=0.42):
     """float64 [order + 1, n_fft/2 + 1] with mc = matrix @ log(P): the unit vectors of log P pushed through irfft, c[0] / 2 and
     the frequency-transform recursion. Host numpy, cached per argument tuple (read-only)."""
-    key = (int(n_fft), int(order), float(alpha))
-    if key not in _matrix_cache:
-        n_fft, order, alpha = key
-        if n_fft < 2 or n_fft % 2 or not 0 <= order <= n_fft // 2 or not abs(alpha) < 1:
-            raise ValueError('sp2mc_matrix: needs an even n_fft >= 2, 0 <= order <= n_fft/2 and |alpha| < 1')
-        nb = n_fft // 2 + 1
-        c = np.fft.irfft(np.eye(nb), n=n_fft, axis=1)[:, :nb].copy()      # row k: the cepstrum of the k-th unit vector of log P
-        c[:, 0] *= 0.5
-        m = np.ascontiguousarray(_freqt(c, order, alpha).T)
-        m.setflags(write=False)
-        _matrix_cache[key] = m
-    return _matrix_cache[key]
-
-
-def _matrix_on(device, n_fft, order, alpha):
-    key = (int(n_fft), int(order), float(alpha), _dev_key(device))
-    if key not in _dev_matrix_cache:
-        _dev_matrix_cache[key] = torch.tensor(sp2mc_matrix(n_fft, order, alpha), device=device)
-    return _dev_matrix_cache[key]
+    return H.host_table(*_mc_table('sp2mc_matrix', n_fft, order, alpha))
 
 
 def sp2mc(power, order=24, alpha=0.42, floor=POWER_FLOOR, layout='fn'):
     """Mel-cepstrum of a power spectrum (device fp32) -> fp32 [..., n_frames, order + 1]; tdvc_sp2mc, one launch.
     layout='fn': power is [n_frames, n_bins] or [B, n_frames, n_bins], the layout of a WORLD envelope (pysptk.sp2mc's argument);
     layout='nf': [B, n_bins, n_frames], the layout of this package's conv STFT. Any strides: nothing is copied. n_bins = n_fft/2 + 1."""
-    _need_cuda('sp2mc', power)
+    H.need_device('sp2mc', power)
     if layout not in ('fn', 'nf') or power.dim() not in (2, 3):
         raise ValueError("sp2mc: power must be [F, N] / [B, F, N] with layout='fn' or [B, N, F] with layout='nf'")
-    p = power.detach()
-    if p.dtype != torch.float32:
-        p = p.float()
+    p = power.detach().float()
     p3 = p[None] if p.dim() == 2 else p
     if layout == 'nf':
         p3 = p3.transpose(1, 2)
     B, F, nb = p3.shape
-    if min(p3.stride()) < 0:
-        p3 = p3.contiguous()
-    mat = _matrix_on(p.device, 2 * (nb - 1), order, alpha)
+    mat = H.device_table(p.device, *_mc_table('sp2mc_matrix', 2 * (nb - 1), order, alpha))
     mc = torch.empty(B, F, order + 1, dtype=torch.float32, device=p.device)
     L.check(L.lib().tdvc_sp2mc(p3.data_ptr(), p3.stride(0), p3.stride(1), p3.stride(2), mat.data_ptr(), B, F, nb, order, float(floor),
-                               mc.data_ptr(), _stream(p)))
+                               mc.data_ptr(), H.stream(p)))
     return mc[0] if power.dim() == 2 else mc
 
 
@@ -138,54 +130,29 @@ class _Stft:
         pad = self.n_fft // 2
         lib = L.lib()
         xp = torch.empty((B, 1, T + 2 * pad), dtype=torch.float32, device=x.device)
-        L.check(lib.tdvc_reflect_pad_fwd(x.data_ptr(), xp.data_ptr(), B, T, pad, _stream(x)))
+        L.check(lib.tdvc_reflect_pad_fwd(x.data_ptr(), xp.data_ptr(), B, T, pad, H.stream(x)))
         spec = ops.conv_fwd_raw(self.spec, xp, ops._xf())
         pw = torch.empty((B, self.Fp, spec.shape[2]), dtype=torch.float32, device=x.device)
-        L.check(lib.tdvc_power_fwd(spec.data_ptr(), pw.data_ptr(), B, self.Fp, spec.shape[2], _stream(x)))
+        L.check(lib.tdvc_power_fwd(spec.data_ptr(), pw.data_ptr(), B, self.Fp, spec.shape[2], H.stream(x)))
         return pw
 
 
 def cheaptrick_mc_matrix(n_fft, order=24, alpha=0.42):
     """float64 [order + 1, n_fft/2 + 1], G = freqt of the unit vectors: the mel-cepstrum of a CheapTrick frame is G @ c' with c' the
     liftered cepstrum, c[0] halved (include/tdvc.h). Host numpy, cached per argument tuple (read-only)."""
-    key = (int(n_fft), int(order), float(alpha))
-    if key not in _ct_matrix_cache:
-        n_fft, order, alpha = key
-        if n_fft < 2 or n_fft % 2 or not 0 <= order <= n_fft // 2 or not abs(alpha) < 1:
-            raise ValueError('cheaptrick_mc_matrix: needs an even n_fft >= 2, 0 <= order <= n_fft/2 and |alpha| < 1')
-        m = np.ascontiguousarray(_freqt(np.eye(n_fft // 2 + 1), order, alpha).T)
-        m.setflags(write=False)
-        _ct_matrix_cache[key] = m
-    return _ct_matrix_cache[key]
-
-
-def _ct_matrix_on(device, n_fft, order, alpha):
-    key = (int(n_fft), int(order), float(alpha), _dev_key(device))
-    if key not in _ct_dev_matrix_cache:
-        _ct_dev_matrix_cache[key] = torch.tensor(cheaptrick_mc_matrix(n_fft, order, alpha), device=device)
-    return _ct_dev_matrix_cache[key]
+    return H.host_table(*_mc_table('cheaptrick_mc_matrix', n_fft, order, alpha))
 
 
 def _cheaptrick(who, signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, want_env, mc_args):
-    """One tdvc_cheaptrick launch -> (env or None, mc or None); mc_args = (order, alpha) or None."""
-    _need_cuda(who, signal, f0)
-    if signal.dim() != 3 or signal.shape[1] != 1:
-        raise ValueError(f'{who}: signal must be [B, 1, T]')
+    """One tdvc_cheaptrick launch -> (env or None, mc or None); mc_args = (order, alpha) or None. The caller has checked signal."""
+    H.need_device(who, f0)
     B, _, T = signal.shape
     if f0.dim() != 2 or f0.shape[0] != B:
         raise ValueError(f'{who}: an F0 track must be [B, n_frames]')
     if n_fft not in CHEAPTRICK_N_FFT:
         raise ValueError(f'{who}: the CheapTrick envelope needs n_fft in {CHEAPTRICK_N_FFT}')
     hop = int(round(sample_rate / 200)) if hop is None else int(hop)
-    x, f = signal.detach(), f0.detach()
-    if x.dtype != torch.float32:
-        x = x.float()
-    if f.dtype != torch.float32:
-        f = f.float()
-    if min(x.stride()) < 0:
-        x = x.contiguous()
-    if min(f.stride()) < 0:
-        f = f.contiguous()
+    x, f = signal.detach().float(), f0.detach().float()
     F, nb, dev = f.shape[1], n_fft // 2 + 1, x.device
     ln = _len_arg(who, lengths, B, dev)
     env = torch.empty(B, F, nb, dtype=torch.float32, device=dev) if want_env else None
@@ -193,11 +160,10 @@ def _cheaptrick(who, signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, wa
     order = 0
     if mc_args is not None:
         order, alpha = mc_args
-        mat = _ct_matrix_on(dev, n_fft, order, alpha)
+        mat = H.device_table(dev, *_mc_table('cheaptrick_mc_matrix', n_fft, order, alpha))
         mc = torch.empty(B, F, order + 1, dtype=torch.float32, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    L.check(L.lib().tdvc_cheaptrick(x.data_ptr(), x.stride(0), x.stride(2), ptr(ln), T, f.data_ptr(), f.stride(0), f.stride(1), B, F, hop,
-                                    int(sample_rate), int(n_fft), float(q1), float(floor), ptr(mat), int(order), ptr(env), ptr(mc), _stream(x)))
+    L.check(L.lib().tdvc_cheaptrick(x.data_ptr(), x.stride(0), x.stride(2), H.ptr(ln), T, f.data_ptr(), f.stride(0), f.stride(1), B, F, hop,
+                                    int(sample_rate), int(n_fft), float(q1), float(floor), H.ptr(mat), int(order), H.ptr(env), H.ptr(mc), H.stream(x)))
     return env, mc
 
 
@@ -210,6 +176,7 @@ def cheaptrick(signal, f0, sample_rate=16000, n_fft=1024, hop=None, q1=-0.15, le
     window repeats the last valid sample, as WORLD does at the end of its input). Any strides: nothing is copied. q1 is the
     lifter's spectral-recovery weight; floor > 0 replaces WORLD's random safeguard (CHEAPTRICK_FLOOR has the reason).
     **Parity with pyworld is unchecked.** n_fft is 512, 1024 or 2048."""
+    _signal3('cheaptrick', signal)
     return _cheaptrick('cheaptrick', signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, True, None)[0]
 
 
@@ -225,31 +192,24 @@ def mel_cepstrum(signal, sample_rate=16000, n_fft=1024, hop=80, order=24, alpha=
     no envelope is stored), fp32 [B, F, order + 1] on the frames of the F0 track f0 [B, F]; f0=None runs
     yin_f0(pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate), as `mcd` does. sample_rate enters the arithmetic, floor
     defaults to CHEAPTRICK_FLOOR, n_fft is 512, 1024 or 2048, and samples at and past lengths[b] are never read."""
-    _need_cuda('mel_cepstrum', signal)
+    _signal3('mel_cepstrum', signal)
     if envelope not in ENVELOPES:
         raise ValueError(f'mel_cepstrum: unknown envelope {envelope!r} (known: {ENVELOPES})')
     if envelope == 'cheaptrick':
-        if signal.dim() != 3 or signal.shape[1] != 1:
-            raise ValueError('mel_cepstrum: signal must be [B, 1, T]')
         if f0 is None:
             from . import pitch
             f0 = pitch.yin_f0(signal.detach().float()[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
         mc = _cheaptrick('mel_cepstrum', signal, f0, sample_rate, n_fft, hop, q1, lengths, CHEAPTRICK_FLOOR if floor is None else floor,
                          False, (order, alpha))[1]
-        if lengths is None:
-            return mc
-        return mc, (1 + torch.div(lengths.to(signal.device), int(hop), rounding_mode='floor')).clamp(0, mc.shape[1]).to(torch.int32)
-    floor = POWER_FLOOR if floor is None else floor
-    if signal.dim() != 3 or signal.shape[1] != 1:
-        raise ValueError('mel_cepstrum: signal must be [B, 1, T]')
-    if n_fft % 2 or n_fft < 4 or hop < 1 or signal.shape[-1] <= n_fft // 2:
-        raise ValueError('mel_cepstrum: needs an even n_fft, hop >= 1 and more than n_fft/2 samples (reflect padding)')
-    key = (int(n_fft), int(hop), _dev_key(signal.device))
-    if key not in _stft_cache:
-        _stft_cache[key] = _Stft(int(n_fft), int(hop), signal.device)
-    st = _stft_cache[key]
-    pw = st.power(signal.detach().float())
-    mc = sp2mc(pw[:, :st.F], order, alpha, floor, layout='nf')
+    else:
+        if n_fft % 2 or n_fft < 4 or hop < 1 or signal.shape[-1] <= n_fft // 2:
+            raise ValueError('mel_cepstrum: needs an even n_fft, hop >= 1 and more than n_fft/2 samples (reflect padding)')
+        key = (int(n_fft), int(hop), H.dev_key(signal.device))
+        if key not in _stft_cache:
+            _stft_cache[key] = _Stft(int(n_fft), int(hop), signal.device)
+        st = _stft_cache[key]
+        pw = st.power(signal.detach().float())
+        mc = sp2mc(pw[:, :st.F], order, alpha, POWER_FLOOR if floor is None else floor, layout='nf')
     if lengths is None:
         return mc
     return mc, (1 + torch.div(lengths.to(signal.device), int(hop), rounding_mode='floor')).clamp(0, mc.shape[1]).to(torch.int32)
@@ -265,19 +225,6 @@ def _len_arg(who, v, B, device):
     return v.to(torch.int32).contiguous()
 
 
-def _frames3(who, t):
-    if t.dim() not in (2, 3):
-        raise ValueError(f'{who}: sequences must be [N, D] or [B, N, D]')
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    t3 = t[None] if t.dim() == 2 else t
-    B, N, D = t3.shape
-    if (D > 1 and t3.stride(2) != 1) or (N > 1 and t3.stride(1) < D) or (B > 1 and t3.stride(0) < 0):
-        t3 = t3.contiguous()
-    return t3, (t3.stride(0) if B > 1 else N * D), (t3.stride(1) if N > 1 else D)
-
-
 def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
     """Exact dynamic time warping of x [B, N, D] against y [B, M, D] (device fp32; [N, D] / [M, D] for one pair) ->
     (cost float64 [B], length int32 [B][, path int64 [B, N + M - 1, 2]]); tdvc_dtw, one launch, no host synchronisation.
@@ -286,14 +233,14 @@ def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
     accumulated cost is float64. Ties: the first minimum in the order up (i-1, j), left (i, j-1), diagonal. length is the number
     of cells of that path, so cost / length is the reference's figure. The path starts at (0, 0) and is padded with -1.
     A pair with a length of 0 gives cost NaN, length 0 and a path of -1. N, M <= 4096 and D <= 64."""
-    _need_cuda('dtw', x, y)
+    H.need_device('dtw', x, y)
     if metric not in METRICS:
         raise ValueError(f'dtw: unknown metric {metric!r} (known: {sorted(METRICS)})')
-    if x.dim() != y.dim():
+    if x.dim() != y.dim() or x.dim() not in (2, 3):
         raise ValueError('dtw: x and y must both be [N, D] or both [B, N, D]')
     single = x.dim() == 2
-    x3, x_bs, x_fs = _frames3('dtw', x)
-    y3, y_bs, y_fs = _frames3('dtw', y)
+    x3, x_bs, x_fs = H.frames3('dtw', x)
+    y3, y_bs, y_fs = H.frames3('dtw', y)
     B, N, D = x3.shape
     if y3.shape[0] != B or y3.shape[2] != D:
         raise ValueError(f'dtw: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in batch or feature size')
@@ -306,10 +253,9 @@ def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
     P = N + M - 1
     path = torch.full((B, max(P, 0), 2), -1, dtype=torch.int32, device=dev) if return_path else None
     nbytes = lib.tdvc_dtw_workspace(B, N, M, int(return_path)) if B > 0 else 0
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)      # caching allocator: graph-safe
-    L.check(lib.tdvc_dtw(x3.data_ptr(), x_bs, x_fs, y3.data_ptr(), y_bs, y_fs, xl.data_ptr() if xl is not None else None,
-                         yl.data_ptr() if yl is not None else None, B, N, M, D, METRICS[metric], cost.data_ptr(), length.data_ptr(),
-                         path.data_ptr() if return_path else None, 2 * P, ws.data_ptr(), nbytes, _stream(x3)))
+    ws = H.scratch(nbytes, dev)
+    L.check(lib.tdvc_dtw(x3.data_ptr(), x_bs, x_fs, y3.data_ptr(), y_bs, y_fs, H.ptr(xl), H.ptr(yl), B, N, M, D, METRICS[metric],
+                         cost.data_ptr(), length.data_ptr(), H.ptr(path), 2 * P, ws.data_ptr(), nbytes, H.stream(x3)))
     if single:
         cost, length, path = cost[0], length[0], (path[0] if return_path else None)
     return (cost, length, path.long()) if return_path else (cost, length)
@@ -395,7 +341,7 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
         diff_f0_mean, diff_f0_var, f0_ratio      `f0_stats` of the two tracks
     Every entry is float64, and every entry is NaN for a pair with fewer than min_voiced voiced frames on either side (the
     reference returns NaN under 10 on the test side). Nothing synchronises with the host."""
-    _need_cuda('mcd', test, ref)
+    H.need_device('mcd', test, ref)
     for s in (test, ref):
         if s.dim() != 3 or s.shape[1] != 1 or s.shape[0] != test.shape[0]:
             raise ValueError('mcd: waveforms must be [B, 1, T] with one batch size')

@@ -13,13 +13,10 @@ import torch
 from torch.autograd import Function
 
 from . import _lib as L
+from ._host import stream as _stream
 from .arena import ConvSlot
 
 SLOPE = 0.2
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 class ConvSpec:

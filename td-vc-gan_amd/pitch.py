@@ -22,6 +22,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import _host as H
 from . import _lib as L
 
 
@@ -48,10 +49,10 @@ class _YinSoftFn(torch.autograd.Function):
         gy = gy.contiguous().float()
         lib = L.lib()
         nbytes = lib.tdvc_yin_soft_bwd_workspace(B, T, tau_max, stride)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x2.device)      # caching allocator: graph-safe
+        ws = H.scratch(nbytes, x2.device)
         dx = torch.empty(B, T, dtype=torch.float32, device=x2.device)      # the kernel writes every element
         L.check(lib.tdvc_yin_soft_bwd(x2.data_ptr(), x_bs, B, T, tau_min, tau_max, stride, float(threshold), float(sample_rate),
-                                      gy.data_ptr(), dx.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(x2.device).cuda_stream))
+                                      gy.data_ptr(), dx.data_ptr(), ws.data_ptr(), nbytes, H.stream(x2)))
         return (dx,) + (None,) * 7
 
 
@@ -64,27 +65,16 @@ def _launch(x2, x_bs, sample_rate, tau_min, tau_max, stride, threshold, soft, re
     f0 = torch.empty(B, max(nf, 0), dtype=torch.float32, device=x2.device)
     cmdf = torch.empty(B, max(nf, 0), max(n, 0), dtype=torch.float32, device=x2.device) if return_cmdf else None
     L.check(lib.tdvc_yin_f0(x2.data_ptr(), x_bs, B, T, tau_min, tau_max, stride, float(threshold), int(bool(soft)), float(sample_rate),
-                            f0.data_ptr(), cmdf.data_ptr() if return_cmdf else None, torch.cuda.current_stream(x2.device).cuda_stream))
+                            f0.data_ptr(), H.ptr(cmdf), H.stream(x2)))
     return f0, cmdf
 
 
 def _yin(x, sample_rate, tau_min, tau_max, stride, threshold, soft, return_cmdf):
     """x [..., T] (device tensor, last axis dense) -> f0 [..., n_frames] (, cmdf [..., n_frames, tau_max - 1 - tau_min])."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise L.TdvcError('yin_f0: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
-    if x.dim() < 1:
-        raise ValueError('yin_f0: signal must be [T], [B, T] or [..., T]')
-    x = x.float()
-    lead, T = x.shape[:-1], x.shape[-1]
-    x2 = x.reshape(-1, T) if x.dim() != 2 else x          # a view wherever the leading axes share one stride
-    if T > 1 and x2.stride(-1) != 1:
-        x2 = x2.contiguous()
-    B = x2.shape[0]
-    x_bs = x2.stride(0) if B > 1 else T
-    if x_bs < 0:
-        x2, x_bs = x2.contiguous(), T
+    H.need_device('yin_f0', x)
+    x2, x_bs, lead = H.rows2('yin_f0', x, any_lead=True, keep_grad=True)
     if soft and x2.requires_grad and torch.is_grad_enabled():
-        # differentiable path: the layout steps above are torch ops, so the gradient returns in the input's shape
+        # differentiable path: the layout steps of rows2 are torch ops, so the gradient returns in the input's shape
         out = _YinSoftFn.apply(x2, x_bs, sample_rate, tau_min, tau_max, stride, threshold, bool(return_cmdf))
         f0, cmdf = out if return_cmdf else (out, None)
     else:
@@ -96,7 +86,6 @@ def _yin(x, sample_rate, tau_min, tau_max, stride, threshold, soft, return_cmdf)
 
 DECODERS = (None, 'viterbi')
 THETA = 100.0      # the reference's own sharpness of the CMDF (util/yin.py:132, _softsearch)
-_transition_cache, _dev_transition_cache = {}, {}
 _checked_bands = {}      # id(lo tensor) -> (version, n, W) it was found in range for; the entry goes when the tensor does
 
 
@@ -106,15 +95,11 @@ def _mark_band_checked(lo, n, W):
     _checked_bands[id(lo)] = (lo._version, n, W)
 
 
-def _dev_key(device):
-    device = torch.device(device)
-    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
-
-
 def _transition_host(tau_min, tau_max, half_width_cents):
     """(logw float64 [n, W], lo int64 [n]) in numpy; see viterbi_transition."""
     key = (int(tau_min), int(tau_max), float(half_width_cents))
-    if key not in _transition_cache:
+
+    def build():
         n = key[1] - 1 - key[0]
         if n < 1 or not key[2] > 0:
             raise ValueError('viterbi_transition: needs tau_max - 1 - tau_min >= 1 states and a positive half width')
@@ -127,8 +112,8 @@ def _transition_host(tau_min, tau_max, half_width_cents):
         with np.errstate(divide='ignore'):
             logw = np.where(band > 0, np.log(band), -np.inf)
         logw.setflags(write=False); lo.setflags(write=False)
-        _transition_cache[key] = (logw, lo)
-    return _transition_cache[key]
+        return logw, lo
+    return H.host_table(('viterbi_transition',) + key, build)
 
 
 def viterbi_transition(tau_min, tau_max, half_width_cents=240.0, device=None):
@@ -139,13 +124,14 @@ def viterbi_transition(tau_min, tau_max, half_width_cents=240.0, device=None):
     and NOT row-normalised: the lag lattice is not uniform in cents, so normalising rows in the lag domain would favour short or
     long lags. Built in numpy float64, rounded once, cached per argument tuple and device."""
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-    key = (int(tau_min), int(tau_max), float(half_width_cents), _dev_key(device))
-    if key not in _dev_transition_cache:
-        logw, lo = _transition_host(tau_min, tau_max, half_width_cents)
+    key = (int(tau_min), int(tau_max), float(half_width_cents))
+
+    def upload(host, device):
+        logw, lo = host
         t = (torch.from_numpy(logw.astype(np.float32)).to(device), torch.from_numpy(lo.astype(np.int32)).to(device))
         _mark_band_checked(t[1], logw.shape[0], logw.shape[1])      # in range by construction
-        _dev_transition_cache[key] = t
-    return _dev_transition_cache[key]
+        return t
+    return H.device_table(device, ('viterbi_transition',) + key, lambda: _transition_host(*key), upload)
 
 
 def viterbi_path(x, logw, lo, scale=1.0, prior=None, jump=math.inf):
@@ -155,12 +141,9 @@ def viterbi_path(x, logw, lo, scale=1.0, prior=None, jump=math.inf):
     logw [n, W] fp32 and lo [n] int32 are a band table such as `viterbi_transition` returns; prior [n] or None; jump = inf
     disables the floor. A lo tensor that did not come from `viterbi_transition` is checked on the host the first time it is seen (one
     synchronisation; pass the same int32 device tensor again and it is not repeated): a band that leaves [0, n) raises ValueError. One launch; not differentiable."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise L.TdvcError('viterbi_path: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
-    if x.dim() < 2:
-        raise ValueError('viterbi_path: lattice must be [F, n] or [..., F, n]')
-    x = x.detach().float()
-    lead, F, n = x.shape[:-2], x.shape[-2], x.shape[-1]
+    H.need_device('viterbi_path', x)
+    x3, x_bs, x_fs = H.frames3('viterbi_path', x)
+    lead, (B, F, n) = x.shape[:-2], x3.shape
     if logw.dim() != 2 or logw.shape[0] != n or lo.shape != (n,):
         raise ValueError(f'viterbi_path: band table {tuple(logw.shape)} / {tuple(lo.shape)} does not match {n} states')
     logw = logw.to(device=x.device, dtype=torch.float32).contiguous()
@@ -174,19 +157,12 @@ def viterbi_path(x, logw, lo, scale=1.0, prior=None, jump=math.inf):
         prior = prior.to(device=x.device, dtype=torch.float32).contiguous()
         if prior.shape != (n,):
             raise ValueError(f'viterbi_path: prior must be [{n}]')
-    x3 = x.reshape(-1, F, n) if x.dim() != 3 else x          # a view wherever the leading axes share one stride
-    B = x3.shape[0]
-    if (n > 1 and x3.stride(2) != 1) or (F > 1 and x3.stride(1) < n) or (B > 1 and x3.stride(0) < 0):
-        x3 = x3.contiguous()
-    x_bs = x3.stride(0) if B > 1 else F * n
-    x_fs = x3.stride(1) if F > 1 else n
     lib = L.lib()
     path = torch.empty(B, F, dtype=torch.int32, device=x.device)
     nbytes = lib.tdvc_viterbi_workspace(B, F, n)
-    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)      # caching allocator: graph-safe
-    L.check(lib.tdvc_viterbi_path(x3.data_ptr(), x_bs, x_fs, float(scale), prior.data_ptr() if prior is not None else None,
-                                  logw.data_ptr(), lo.data_ptr(), W, float(jump), B, F, n, path.data_ptr(), F, ws.data_ptr(), nbytes,
-                                  torch.cuda.current_stream(x.device).cuda_stream))
+    ws = H.scratch(nbytes, x.device)
+    L.check(lib.tdvc_viterbi_path(x3.data_ptr(), x_bs, x_fs, float(scale), H.ptr(prior), logw.data_ptr(), lo.data_ptr(), W, float(jump),
+                                  B, F, n, path.data_ptr(), F, ws.data_ptr(), nbytes, H.stream(x)))
     return path.reshape(*lead, F).long()
 
 
@@ -202,14 +178,11 @@ def _viterbi_f0(x, sample_rate, tau_min, tau_max, stride, threshold, octave_cost
     hard, cmdf = _yin(x, sample_rate, tau_min, tau_max, stride, threshold, False, True)
     n = cmdf.shape[-1]
     logw, lo = viterbi_transition(tau_min, tau_max, device=cmdf.device)
-    key = ('prior', tau_min, tau_max, float(octave_cost), _dev_key(cmdf.device))
-    if key not in _dev_transition_cache:
-        lag = np.arange(n, dtype=np.float64) + tau_min + 1
-        _dev_transition_cache[key] = torch.from_numpy((-float(octave_cost) * np.log2(lag / (tau_min + 1))).astype(np.float32)).to(cmdf.device)
-    path = viterbi_path(cmdf, logw, lo, scale=-THETA, prior=_dev_transition_cache[key], jump=float(jump_cost))
+    prior = H.device_table(cmdf.device, ('viterbi prior', tau_min, tau_max, float(octave_cost)), lambda: (
+        -float(octave_cost) * np.log2((np.arange(n, dtype=np.float64) + tau_min + 1) / (tau_min + 1))).astype(np.float32))
+    path = viterbi_path(cmdf, logw, lo, scale=-THETA, prior=prior, jump=float(jump_cost))
     f0 = torch.where(hard != 0, sample_rate / (path + (tau_min + 1)).to(torch.float32), torch.zeros_like(hard))
     return (f0, cmdf) if return_cmdf else f0
-
 
 
 def yin_f0(signal, sample_rate, pitch_min=20, pitch_max=20000, frame_stride=0.01, threshold=0.1, soft=False, return_cmdf=False,

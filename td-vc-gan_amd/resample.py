@@ -34,6 +34,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
+from . import _host as H
 from . import _lib as L
 
 FILTERS = {      # name -> (num_zeros, precision, beta, rolloff): the parameters resampy's two shipped tables were made with
@@ -48,16 +49,7 @@ TO = L.RESAMPLE_TO
 Bank = collections.namedtuple('Bank', 'bank L M left')           # bank float64 [L][W]
 Lengths = collections.namedtuple('Lengths', 'dev host')          # int32 device tensor [B], list of int
 
-_table_cache, _bank_cache, _dev_bank_cache, _len_cache = {}, {}, {}, {}
-
-
-def _need_device(t, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.TdvcError(f'{what}: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
-
-
-def _dev_key(device):
-    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+_len_cache = {}
 
 
 def resample_filter(filter='kaiser_best'):
@@ -71,13 +63,14 @@ def resample_filter(filter='kaiser_best'):
         return win, int(precision)
     if filter not in FILTERS:
         raise ValueError(f'resample_filter: unknown filter {filter!r} (known: {sorted(FILTERS)}, or a (table, precision) pair)')
-    if filter not in _table_cache:
+
+    def build():
         num_zeros, precision, beta, rolloff = FILTERS[filter]
         n = num_zeros * 2 ** precision
         win = rolloff * np.sinc(rolloff * np.linspace(0, num_zeros, n + 1)) * np.kaiser(2 * n + 1, beta)[n:]
         win.setflags(write=False)
-        _table_cache[filter] = (win, precision)
-    return _table_cache[filter]
+        return win, precision
+    return H.host_table(('resample_filter', filter), build)
 
 
 def _filter_key(filter):
@@ -103,9 +96,10 @@ def resample_bank(sr_orig, sr_new, filter='kaiser_best'):
     of phase p = (t*M) mod L, so that y[t] = sum_j bank[p][j] * x[(t*M) div L - left + 1 + j] with x zero outside the row.
     ValueError when the bank would exceed 8 MiB."""
     sr_orig, sr_new = _rates(sr_orig, sr_new)
-    key = (sr_orig, sr_new, _filter_key(filter))
-    if key in _bank_cache:
-        return _bank_cache[key]
+    return H.host_table(('resample_bank', sr_orig, sr_new, _filter_key(filter)), lambda: _build_bank(sr_orig, sr_new, filter))
+
+
+def _build_bank(sr_orig, sr_new, filter):
     win, precision = resample_filter(filter)
     fr = Fraction(sr_new, sr_orig)
     Lp, M = fr.numerator, fr.denominator
@@ -137,47 +131,28 @@ def resample_bank(sr_orig, sr_new, filter='kaiser_best'):
         k = off2 + step * np.arange(cnt2)
         bank[p, left:left + cnt2] = win[k] + eta2 * delta[k]
     bank.setflags(write=False)
-    _bank_cache[key] = Bank(bank, Lp, M, left)
-    return _bank_cache[key]
+    return Bank(bank, Lp, M, left)
 
 
 def _device_bank(sr_orig, sr_new, filter, device):
     """The bank in the kernel's layout, float64 [W][L] with column q = t mod L holding phase (q*M) mod L, uploaded once per rate
     pair, filter and device: a repeated call copies nothing from the host."""
-    key = (int(sr_orig), int(sr_new), _filter_key(filter), _dev_key(device))
-    if key not in _dev_bank_cache:
-        bk = resample_bank(sr_orig, sr_new, filter)
+    def upload(bk, device):
         order = (np.arange(bk.L, dtype=np.int64) * bk.M) % bk.L
-        _dev_bank_cache[key] = (torch.from_numpy(np.ascontiguousarray(bk.bank[order].T)).to(device), bk)
-    return _dev_bank_cache[key]
+        return torch.from_numpy(np.ascontiguousarray(bk.bank[order].T)).to(device), bk
+    return H.device_table(device, ('resample_bank', sr_orig, sr_new, _filter_key(filter)), lambda: _build_bank(sr_orig, sr_new, filter), upload)
 
 
 def _device_lengths(values, device):
     """Host lengths as an int32 device tensor. Cached by value, so a batch geometry that comes back (every fixed-length batch, and a
     captured graph's warm-up) uploads nothing the second time."""
-    key = (_dev_key(device), tuple(values))
+    key = (H.dev_key(device), tuple(values))
     t = _len_cache.get(key)
     if t is None:
         if len(_len_cache) >= 1024:
             _len_cache.clear()
         t = _len_cache[key] = torch.tensor(list(values), dtype=torch.int32).to(device)
     return t
-
-
-def _rows(signal, what):
-    """signal [T], [B, T] or [B, 1, T] -> (x2 [B, T] fp32 with a dense last axis, row stride in elements, leading shape)"""
-    if signal.dim() not in (1, 2, 3) or (signal.dim() == 3 and signal.shape[1] != 1):
-        raise ValueError(f'{what}: signal must be [T], [B, T] or [B, 1, T]')
-    x = signal.detach().float()
-    T = x.shape[-1]
-    x2 = x[:, 0] if x.dim() == 3 else x.reshape(1, T) if x.dim() == 1 else x
-    if T > 1 and x2.stride(-1) != 1:
-        x2 = x2.contiguous()
-    B = x2.shape[0]
-    x_bs = x2.stride(0) if B > 1 else T
-    if x_bs < 0:
-        x2, x_bs = x2.contiguous(), T
-    return x2, x_bs, tuple(x.shape[:-1])
 
 
 def _host_lengths(lengths, B, T, what):
@@ -208,11 +183,9 @@ def _resample_rows(x2, x_bs, n_in, sr_orig, sr_new, filter):
     nbytes = lib.tdvc_resample_workspace(B, n_max)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     W = bank_d.shape[0]
-    rc = lib.tdvc_resample(x2.data_ptr(), x_bs, _device_lengths(n_in, dev).data_ptr(), n_out_d.data_ptr(), B, T, n_max, bank_d.data_ptr(),
-                           bk.L, 1, bk.L, bk.M, W, bk.left, y.data_ptr(), n_max, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-    if rc == L.EUNSUPPORTED:
-        raise ValueError(f'resample: {lib.tdvc_last_error().decode()}')
-    L.check(rc)
+    H.check('resample', lib.tdvc_resample(x2.data_ptr(), x_bs, _device_lengths(n_in, dev).data_ptr(), n_out_d.data_ptr(), B, T, n_max,
+                                          bank_d.data_ptr(), bk.L, 1, bk.L, bk.M, W, bk.left, y.data_ptr(), n_max, ws.data_ptr(), nbytes,
+                                          H.stream(y)))
     return y, Lengths(n_out_d, n_out), ws.view(B, -1)
 
 
@@ -222,9 +195,9 @@ def resample(signal, sr_orig, sr_new, lengths=None, filter='kaiser_best'):
     lengths: host sequence of valid samples per row (default: all T); samples past a row's length are never read.
     filter: 'kaiser_best' (resampy's default), 'kaiser_fast', or a (table, precision) pair. Equal rates return the input itself with
     no launch. float64 accumulation, rounded once; bit-identical from call to call; no host synchronisation."""
-    _need_device(signal, 'resample')
+    H.need_device('resample', signal)
     sr_orig, sr_new = _rates(sr_orig, sr_new)
-    x2, x_bs, lead = _rows(signal, 'resample')
+    x2, x_bs, lead = H.rows2('resample', signal)
     n_in = _host_lengths(lengths, x2.shape[0], x2.shape[1], 'resample')
     if sr_orig == sr_new:
         return signal, Lengths(_device_lengths(n_in, signal.device), n_in)
@@ -275,12 +248,12 @@ def load_segments(signals, lengths, sr_orig, sample_rate=16000, normalization_db
     normal; by default they are drawn on the device with `generator`, the start uniformly among the windows that hold a non-zero
     sample. info: n_out (host list), n_out_dev, start, gain (float64 [B], the rms gain), aug_gain, aug_sign, noise. One resample
     launch and one tdvc_segment launch; no host synchronisation."""
-    _need_device(signals, 'load_segments')
+    H.need_device('load_segments', signals)
     if signals.dim() != 2:
         raise ValueError('load_segments: signals must be a padded [B, Tmax] batch')
     sr_orig, sample_rate = _rates(sr_orig, sample_rate)
     dev = signals.device
-    x2, x_bs, _ = _rows(signals, 'load_segments')
+    x2, x_bs, _ = H.rows2('load_segments', signals)
     B = x2.shape[0]
     n_in = _host_lengths(lengths, B, x2.shape[1], 'load_segments')
     if sr_orig == sample_rate:
@@ -318,12 +291,11 @@ def load_segments(signals, lengths, sr_orig, sample_rate=16000, normalization_db
         noise = None
     out = torch.empty(B, 1, S, dtype=torch.float32, device=dev)      # the kernel writes every element
     gain = torch.ones(B, dtype=torch.float64, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    L.check(L.lib().tdvc_segment(y.data_ptr() if y.numel() else out.data_ptr(), y_bs, n.dev.data_ptr(), B, n_max, ptr(tile_sq),
-                                 tile_sq.shape[1] if tile_sq is not None else 0, ptr(start), ptr(aug_gain), ptr(aug_sign), ptr(noise), S,
-                                 float(augment_noise) if augment_noise is not None else 0.0, int(bool(normalization_db)),
-                                 float(normalization_db or 0.0), ms, S, out.data_ptr(), gain.data_ptr(),
-                                 torch.cuda.current_stream(dev).cuda_stream))
+    L.check(L.lib().tdvc_segment(y.data_ptr() if y.numel() else out.data_ptr(), y_bs, n.dev.data_ptr(), B, n_max, H.ptr(tile_sq),
+                                 tile_sq.shape[1] if tile_sq is not None else 0, H.ptr(start), H.ptr(aug_gain), H.ptr(aug_sign),
+                                 H.ptr(noise), S, float(augment_noise) if augment_noise is not None else 0.0,
+                                 int(bool(normalization_db)), float(normalization_db or 0.0), ms, S, out.data_ptr(), gain.data_ptr(),
+                                 H.stream(out)))
     return out, dict(n_out=n.host, n_out_dev=n.dev, start=start, gain=gain, aug_gain=aug_gain, aug_sign=aug_sign, noise=noise)
 
 

@@ -3,6 +3,7 @@ import math
 
 import torch
 
+from . import _host as H
 from . import _lib as L
 
 
@@ -14,8 +15,7 @@ def f0_to_excitation(f0, step_size, sampling_rate=16000, linear=True, noise=None
     standard-normal tensors [B, 1, T], `start_phase` = 1-element tensor in radians) so that both sides of a parity test use
     the same draw; by default they are drawn on the device with torch's generator.
     """
-    if not f0.is_cuda:
-        raise L.TdvcError('f0_to_excitation: the HIP path needs a CUDA/ROCm tensor (there is no CPU fallback)')
+    H.need_device('f0_to_excitation', f0)
     f0 = f0.contiguous().float()
     B, one, nf = f0.shape
     if one != 1 or nf < 2:
@@ -30,8 +30,7 @@ def f0_to_excitation(f0, step_size, sampling_rate=16000, linear=True, noise=None
     start_phase = start_phase.reshape(1).contiguous().float()
     exc = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
     L.check(L.lib().tdvc_f0_to_excitation(f0.data_ptr(), nv.data_ptr(), nu.data_ptr(), start_phase.data_ptr(), exc.data_ptr(),
-                                          B, nf, int(step_size), float(sampling_rate), int(bool(linear)),
-                                          torch.cuda.current_stream(dev).cuda_stream))
+                                          B, nf, int(step_size), float(sampling_rate), int(bool(linear)), H.stream(exc)))
     return exc
 
 

@@ -18,11 +18,9 @@ Shapes: 16 x 4.48 s (71680 samples, 896 frames at the 5 ms hop) and 1 x 20 s (40
 tools/bench_mcd.py. Device time from events around `iters` back-to-back calls after a warm-up, the implementations alternating in
 rounds; the median round is reported with the spread. One JSON line per shape, microseconds per call.
 """
-import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -31,6 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+from _timing import measure, parse_args, report  # noqa: E402
 
 
 def _lin(y, p):
@@ -76,25 +75,8 @@ def torch_cheaptrick(x, f0, fs, n_fft, hop, q1=-0.15, floor=1e-16):
     return torch.exp(torch.fft.rfft(torch.cat([c, c[..., 1:h].flip(-1)], -1)).real), c
 
 
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--torch-iters', type=int, default=3)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_cheaptrick: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_cheaptrick', iters=20, warmup=3, rounds=5, torch_iters=3)
     import tdvc_amd as P
     from bench_mcd import voiced_signal
     dev = torch.device('cuda:0')
@@ -121,21 +103,10 @@ def main():
         env = E.cheaptrick(test, f0, fs, n_fft).double()
         gap = float(((env - stock()[0]).abs() / env).max())
         r_ct, r_st = E.mcd(test, ref, envelope='cheaptrick'), E.mcd(test, ref)
-        for fn, _ in fns.values():
-            for _ in range(a.warmup if fn is not stock else 1):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(a.rounds):
-            for k, (fn, iters) in fns.items():
-                times[k].append(time_calls(fn, iters))
-        med = {k: statistics.median(v) for k, v in times.items()}
+        med, mm = measure(fns, a.warmup, a.rounds, once=('torch_cheaptrick',))
         out = {'shape': name, 'B': B, 'frames': f0.shape[1], 'n_fft': n_fft, 'voiced_frames': [int(v) for v in (f0 > 0).sum(1).tolist()][:4],
                'torch_env_rel_gap': float(f'{gap:.2e}'), 'mcd_cheaptrick': [round(float(v), 4) for v in r_ct['mcd'].tolist()][:4],
-               'mcd_stft': [round(float(v), 4) for v in r_st['mcd'].tolist()][:4]}
-        for k, v in times.items():
-            out[f'{k}_us'] = round(med[k], 1)
-            out[f'{k}_us_min_max'] = [round(min(v), 1), round(max(v), 1)]
+               'mcd_stft': [round(float(v), 4) for v in r_st['mcd'].tolist()][:4], **report(med, mm, 1)}
         out['us_per_frame'] = round(med['cheaptrick'] / (B * f0.shape[1]), 3)
         out['torch_over_cheaptrick'] = round(med['torch_cheaptrick'] / med['cheaptrick'], 1)
         out['mc_fused_over_mc_stft'] = round(med['mc_fused'] / med['mc_stft'], 2)

@@ -11,7 +11,6 @@ route is timed with a wall clock over whole batches, median of `rounds`. One JSO
 microseconds per call for both, their ratio, the device call's share of a 52 ms train step, and the audio seconds per second of
 one GPU / one CPU worker.
 """
-import argparse
 import json
 import os
 import statistics
@@ -26,19 +25,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import tdvc_amd as P  # noqa: E402
 import peq_ref as PR  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 STEP_MS = 52.0
 SR = 16000
-
-
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
 
 
 def cpu_route(x, G, z, dev):
@@ -55,14 +45,7 @@ def cpu_route(x, G, z, dev):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=200)
-    ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'corrupt_bench.txt'))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_corrupt: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_corrupt', iters=200, warmup=20, rounds=5, out=os.path.join(ROOT, 'profiles', 'corrupt_bench.txt'))
     try:
         import scipy.signal  # noqa: F401
         have_scipy = True
@@ -76,19 +59,11 @@ def main():
         G, z = rng.uniform(-12, 12, (B, 10)), rng.uniform(0, 1, (B, 10))
         xd, Gd, zd = torch.from_numpy(x).to(dev), torch.from_numpy(G).to(dev), torch.from_numpy(z).to(dev)
         sos = P.corrupt.peq_sos(Gd, torch.from_numpy(PR.q_of_z(z)).to(dev))
-        full = lambda: P.corrupt.random_eq(xd, gains_db=Gd, z=zd)
-        filt = lambda: P.corrupt.sos_filter(xd, sos, match_rms=True)
-        for _ in range(a.warmup):
-            full(); filt()
-        torch.cuda.synchronize()
-        tf, tk = [], []
-        for _ in range(a.rounds):
-            tf.append(time_calls(full, a.iters))
-            tk.append(time_calls(filt, a.iters))
-        mf, mk = statistics.median(tf), statistics.median(tk)
-        rec = {'shape': name, 'random_eq_us': round(mf, 2), 'random_eq_us_min_max': [round(min(tf), 2), round(max(tf), 2)],
-               'sos_filter_us': round(mk, 2), 'sos_filter_us_min_max': [round(min(tk), 2), round(max(tk), 2)],
-               'share_of_52ms_step': round(mf / (STEP_MS * 1e3), 5), 'gpu_audio_s_per_s': round(B * T / SR / (mf * 1e-6), 1)}
+        fns = {'random_eq': (lambda: P.corrupt.random_eq(xd, gains_db=Gd, z=zd), a.iters),
+               'sos_filter': (lambda: P.corrupt.sos_filter(xd, sos, match_rms=True), a.iters)}
+        med, mm = measure(fns, a.warmup, a.rounds)
+        mf = med['random_eq']
+        rec = {'shape': name, **report(med, mm, 2), 'share_of_52ms_step': round(mf / (STEP_MS * 1e3), 5), 'gpu_audio_s_per_s': round(B * T / SR / (mf * 1e-6), 1)}
         if have_scipy:
             cpu_route(x, G, z, dev)
             tc = []

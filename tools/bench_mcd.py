@@ -15,7 +15,6 @@ frames). The signals are harmonic tones with vibrato, voiced throughout, so near
 alignment inside `mcd` is close to full size. Device time from events around `iters` back-to-back calls after a warm-up, the
 implementations alternating in rounds; the median round is reported with the spread. One JSON line per shape, microseconds per call.
 """
-import argparse
 import json
 import os
 import statistics
@@ -30,6 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import tdvc_amd as P  # noqa: E402
 import dtw_ref as DR  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 
 def torch_dtw_plan(N, M, device):
@@ -76,26 +76,8 @@ def voiced_signal(rng, B, T, sr=16000):
     return torch.from_numpy(np.stack(rows).astype(np.float32))[:, None]
 
 
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--torch-iters', type=int, default=1)
-    ap.add_argument('--host-rounds', type=int, default=3)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_mcd: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_mcd', iters=20, warmup=3, rounds=5, torch_iters=1, host_rounds=3)
     dev = torch.device('cuda:0')
     E = P.evaluate
     hp = P.hparams.HParam(os.path.join(ROOT, 'config', 'conv_enc-stage1.yaml'))
@@ -121,14 +103,7 @@ def main():
         cost, length = dtw()
         agree = float((cost - stock()).abs().max() / cost.abs().max())
         r = whole()
-        for fn, _ in fns.values():
-            for _ in range(a.warmup if fn is not stock else 1):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(a.rounds):
-            for k, (fn, iters) in fns.items():
-                times[k].append(time_calls(fn, iters))
+        med, mm = measure(fns, a.warmup, a.rounds, once=('torch_dtw',))
         xh, yh = mt.cpu().numpy(), mr.cpu().numpy()
         host = []
         for _ in range(a.host_rounds):
@@ -136,13 +111,9 @@ def main():
             hres = host_dtw(xh, yh)
             host.append((time.perf_counter() - t0) * 1e6)
         host_gap = max(abs(float(cost[b]) - hres[b][0]) / hres[b][0] for b in range(B))
-        med = {k: statistics.median(v) for k, v in times.items()}
         out = {'shape': name, 'B': B, 'frames': N, 'D': mt.shape[2], 'voiced_frames_test': [int(v) for v in r['n_test'].tolist()][:4],
                'torch_cost_rel_gap': float(f'{agree:.2e}'), 'host_cost_rel_gap': float(f'{host_gap:.2e}'),
-               'path_len_equals_host': all(int(length[b]) == int(hres[b][1]) for b in range(B))}
-        for k, v in times.items():
-            out[f'{k}_us'] = round(med[k], 1)
-            out[f'{k}_us_min_max'] = [round(min(v), 1), round(max(v), 1)]
+               'path_len_equals_host': all(int(length[b]) == int(hres[b][1]) for b in range(B)), **report(med, mm, 1)}
         out['host_dtw_us'] = round(statistics.median(host), 1)
         out['host_dtw_us_min_max'] = [round(min(host), 1), round(max(host), 1)]
         out['torch_over_dtw'] = round(med['torch_dtw'] / med['dtw'], 1)

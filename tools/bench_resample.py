@@ -11,10 +11,8 @@ maximum. The variants are timed interleaved, round by round, in one process. --s
 figures to: measure it with bench.py in the same session and pass its ms_per_step (without it no share is reported). One JSON line
 per shape, also written to --out.
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -26,18 +24,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import tdvc_amd as P  # noqa: E402
 import resample_ref as RR  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 SR = 16000
-
-
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
 
 
 def torch_route(x, bk, n_out):
@@ -83,16 +72,9 @@ def gather_route(x, bk, lengths, n_out):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=100)
-    ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--torch-iters', type=int, default=5, help='calls per round of the stock-torch route (L convolutions per call)')
-    ap.add_argument('--step-ms', type=float, default=None, help='ms per train step from bench.py, measured in the same session')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'resample_bench.txt'))
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_resample: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_resample', iters=100, warmup=10, rounds=5, torch_iters=5, out=os.path.join(ROOT, 'profiles', 'resample_bench.txt'),
+                   more=lambda ap: ap.add_argument('--step-ms', type=float, default=None,
+                                                   help='ms per train step from bench.py, measured in the same session'))
     dev = torch.device('cuda:0')
     lines = []
     for name, B, sr, secs in (('16x3s_48k', 16, 48000, 3.0), ('16x3s_44k1', 16, 44100, 3.0), ('1x10s_48k', 1, 48000, 10.0)):
@@ -110,22 +92,12 @@ def main():
         y = res()[0]
         assert torch.equal(gather(), y)
         diff = float((stock() - y).abs().max() / y.abs().max())          # the two routes compute the same thing
-        for _ in range(a.warmup):
-            res(); seg(); gather()
-        stock()
-        torch.cuda.synchronize()
-        tr, ts, tt, tg = [], [], [], []
-        for _ in range(a.rounds):
-            tr.append(time_calls(res, a.iters))
-            ts.append(time_calls(seg, a.iters))
-            tt.append(time_calls(stock, a.torch_iters))
-            tg.append(time_calls(gather, a.iters))
-        mr, ms_, mt = statistics.median(tr), statistics.median(ts), statistics.median(tt)
-        mm = lambda v: [round(min(v), 2), round(max(v), 2)]
-        rec = {'shape': name, 'L': bk.L, 'M': bk.M, 'W': int(bk.bank.shape[1]), 'resample_us': round(mr, 2), 'resample_us_min_max': mm(tr),
-               'load_segments_us': round(ms_, 2), 'load_segments_us_min_max': mm(ts), 'torch_fp64_conv1d_us': round(mt, 2),
-               'torch_fp64_conv1d_us_min_max': mm(tt), 'torch_over_hip': round(mt / mr, 2), 'torch_vs_hip_max_rel_diff': diff,
-               'resample_phase_major_bank_us': round(statistics.median(tg), 2), 'resample_phase_major_bank_us_min_max': mm(tg),
+        fns = {'resample': (res, a.iters), 'load_segments': (seg, a.iters), 'torch_fp64_conv1d': (stock, a.torch_iters),
+               'resample_phase_major_bank': (gather, a.iters)}
+        med, mm = measure(fns, a.warmup, a.rounds, once=('torch_fp64_conv1d',))
+        mr, ms_, mt = med['resample'], med['load_segments'], med['torch_fp64_conv1d']
+        rec = {'shape': name, 'L': bk.L, 'M': bk.M, 'W': int(bk.bank.shape[1]), **report(med, mm, 2, ('resample', 'load_segments', 'torch_fp64_conv1d')),
+               'torch_over_hip': round(mt / mr, 2), 'torch_vs_hip_max_rel_diff': diff, **report(med, mm, 2, ('resample_phase_major_bank',)),
                'audio_s_per_s': round(B * secs / (ms_ * 1e-6), 1)}
         if a.step_ms:
             rec.update({'step_ms': a.step_ms, 'resample_share_of_step': round(mr / (a.step_ms * 1e3), 5),

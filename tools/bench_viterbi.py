@@ -13,10 +13,8 @@ decoded track has to cost less than that, or inference time doubles. Device time
 after a warm-up, the implementations alternating in rounds so that drift hits all of them; the median round is reported with
 the spread. One JSON line per shape, microseconds per call.
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -25,6 +23,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tdvc_amd as P  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 
 def torch_viterbi(x, logw, lo, scale, prior, jump):
@@ -47,25 +46,8 @@ def torch_viterbi(x, logw, lo, scale, prior, jump):
     return path
 
 
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=50)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--rounds', type=int, default=5)
-    ap.add_argument('--torch-iters', type=int, default=2)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_viterbi: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_viterbi', iters=50, warmup=5, rounds=5, torch_iters=2)
     dev = torch.device('cuda:0')
     Pt = P.pitch
     shapes = [('16x16000 speech', 16, 16000, 60, 500, 64), ('16x16000 default', 16, 16000, 20, 20000, 160), ('1x71680 speech', 1, 71680, 60, 500, 64)]
@@ -98,19 +80,9 @@ def main():
             noise = (torch.randn(1, 1, T, device=dev), torch.randn(1, 1, T, device=dev))
             phi0 = torch.tensor([0.5], device=dev)
             fns['generator_forward'] = (lambda: P.infer.convert(G, x, c_tgt, f0, noise=noise, start_phase=phi0), a.iters)
-        for fn, _ in fns.values():
-            for _ in range(a.warmup if fn is not stock else 1):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in fns}
-        for _ in range(a.rounds):
-            for k, (fn, iters) in fns.items():
-                times[k].append(time_calls(fn, iters))
-        med = {k: statistics.median(v) for k, v in times.items()}
-        out = {'shape': name, 'B': B, 'frames': cmdf.shape[1], 'n': n, 'W': logw.shape[1], 'torch_path_agreement': round(agree, 4)}
-        for k, v in times.items():
-            out[f'{k}_us'] = round(med[k], 1)
-            out[f'{k}_us_min_max'] = [round(min(v), 1), round(max(v), 1)]
+        med, mm = measure(fns, a.warmup, a.rounds, once=('torch_decode',))
+        out = {'shape': name, 'B': B, 'frames': cmdf.shape[1], 'n': n, 'W': logw.shape[1], 'torch_path_agreement': round(agree, 4),
+               **report(med, mm, 1)}
         out['decode_us_per_frame'] = round(med['decode'] / cmdf.shape[1], 3)
         out['viterbi_over_plain'] = round(med['track_viterbi'] / med['track_plain'], 2)
         out['torch_over_decode'] = round(med['torch_decode'] / med['decode'], 1)

@@ -9,10 +9,8 @@ implementations alternating in rounds so that drift hits both; the median round 
 shape: microseconds per call for both, their ratio, the kernel's share of a 52 ms train step, and the direct sum's arithmetic
 rate (subtract + FMA per term = 3 flop, terms counted from the shape).
 """
-import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -21,6 +19,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tdvc_amd as P  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 STEP_MS = 52.0
 
@@ -47,24 +46,8 @@ def fft_yin(x, sample_rate, pitch_min, pitch_max, frame_stride, threshold=0.1):
     return torch.where(t > 0, sample_rate / (t + tau_min + 1).float(), 0.0)
 
 
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=200)
-    ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--rounds', type=int, default=5)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_yin: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_yin', iters=200, warmup=20, rounds=5)
     dev = torch.device('cuda:0')
     shapes = [('16x16000 speech', 16, 16000, 60, 500, 64 / 16000), ('16x16000 default', 16, 16000, 20, 20000, 0.01),
               ('1x71680 speech', 1, 71680, 60, 500, 64 / 16000)]
@@ -72,22 +55,14 @@ def main():
         g = torch.Generator().manual_seed(0)
         x = (0.03 * torch.randn(B, T, generator=g)).to(dev)
         kw = dict(sample_rate=16000, pitch_min=pmin, pitch_max=pmax, frame_stride=fs)
-        hip = lambda: P.pitch.yin_f0(x, **kw)
-        fft = lambda: fft_yin(x, **kw)
-        for _ in range(a.warmup):
-            hip(); fft()
-        torch.cuda.synchronize()
-        th, tf = [], []
-        for _ in range(a.rounds):
-            th.append(time_calls(hip, a.iters))
-            tf.append(time_calls(fft, a.iters))
+        fns = {'hip': (lambda: P.pitch.yin_f0(x, **kw), a.iters), 'torch_fft': (lambda: fft_yin(x, **kw), a.iters)}
+        med, mm = measure(fns, a.warmup, a.rounds)
         tau_max, stride = int(16000 / pmin), int(fs * 16000)
         L = 2 * tau_max
         nf = (max(T, L) - 1) // stride + 1
         terms = B * nf * sum(L - tau for tau in range(tau_max))
-        mh, mf = statistics.median(th), statistics.median(tf)
-        print(json.dumps({'shape': name, 'frames': B * nf, 'tau_max': tau_max, 'hip_us': round(mh, 2), 'hip_us_min_max': [round(min(th), 2), round(max(th), 2)],
-                          'torch_fft_us': round(mf, 2), 'torch_fft_us_min_max': [round(min(tf), 2), round(max(tf), 2)],
+        mh, mf = med['hip'], med['torch_fft']
+        print(json.dumps({'shape': name, 'frames': B * nf, 'tau_max': tau_max, **report(med, mm, 2),
                           'fft_over_hip': round(mf / mh, 2), 'hip_share_of_52ms_step': round(mh / (STEP_MS * 1e3), 5),
                           'direct_sum_terms': terms, 'hip_tflops_direct_sum': round(3 * terms / mh / 1e6, 2)}), flush=True)
 

@@ -12,11 +12,9 @@ microseconds for the forward, for the backward's two launches (upstream gradient
 forward + backward of f0_yin_loss, and that term's share of a 52 ms train step (target < 1 %; speech hop only: the loss works on the
 [B, 1, T // hop + 1] track layout).
 """
-import argparse
 import json
 import math
 import os
-import statistics
 import sys
 
 import torch
@@ -24,6 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tdvc_amd as P  # noqa: E402
+from _timing import measure, parse_args, report  # noqa: E402
 
 STEP_MS = 52.0
 
@@ -37,24 +36,8 @@ def tone(B, T, sr=16000, seed=0):
     return (0.03 * x).float()
 
 
-def time_calls(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / iters          # microseconds per call
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--iters', type=int, default=200)
-    ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--rounds', type=int, default=5)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_yin_bwd: needs a GPU (a CPU timing says nothing about the kernel)')
+    a = parse_args('bench_yin_bwd', iters=200, warmup=20, rounds=5)
     dev = torch.device('cuda:0')
     L, lib = P._lib, P._lib.lib()
     shapes = [('16x16000 speech', 16, 16000, 60, 500, 64), ('16x16000 default', 16, 16000, 20, 20000, 160), ('1x71680 speech', 1, 71680, 60, 500, 64)]
@@ -73,7 +56,7 @@ def main():
         fwd = lambda: P.pitch.yin_f0(x, soft=True, **kw)
         bwd = lambda: L.check(lib.tdvc_yin_soft_bwd(x.data_ptr(), T, B, T, tau_min, tau_max, stride, 0.1, float(sr), gy.data_ptr(), dx.data_ptr(),
                                                     ws.data_ptr(), nb, st))
-        variants = {'fwd': fwd, 'bwd': bwd}
+        variants = {'fwd': (fwd, a.iters), 'bwd': (bwd, a.iters)}
         if stride == 64:
             xr = x[:, None].clone().requires_grad_()
             tgt = torch.full((B, 1, T // 64 + 1), 150.0, device=dev)
@@ -81,22 +64,12 @@ def main():
             def term():
                 xr.grad = None
                 P.losses.f0_yin_loss(xr, tgt, pitch_min=pmin, pitch_max=pmax).backward()
-            variants['term'] = term
-        for _ in range(a.warmup):
-            for fn in variants.values():
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in variants}
-        for _ in range(a.rounds):
-            for k, fn in variants.items():
-                times[k].append(time_calls(fn, a.iters))
-        med = {k: statistics.median(v) for k, v in times.items()}
+            variants['term'] = (term, a.iters)
+        med, mm = measure(variants, a.warmup, a.rounds)
         out = {'shape': name, 'frames': B * nf, 'tau_max': tau_max, 'frames_on': round(float((f0 > 0).float().mean()), 3),
-               'workspace_mb': round(nb / 1e6, 2), 'fwd_us': round(med['fwd'], 2), 'fwd_us_min_max': [round(min(times['fwd']), 2), round(max(times['fwd']), 2)],
-               'bwd_us': round(med['bwd'], 2), 'bwd_us_min_max': [round(min(times['bwd']), 2), round(max(times['bwd']), 2)],
-               'bwd_over_fwd': round(med['bwd'] / med['fwd'], 2)}
+               'workspace_mb': round(nb / 1e6, 2), **report(med, mm, 2, ('fwd', 'bwd')), 'bwd_over_fwd': round(med['bwd'] / med['fwd'], 2)}
         if 'term' in med:
-            out.update({'term_fwd_bwd_us': round(med['term'], 2), 'term_us_min_max': [round(min(times['term']), 2), round(max(times['term']), 2)],
+            out.update({'term_fwd_bwd_us': round(med['term'], 2), 'term_us_min_max': [round(v, 2) for v in mm['term']],
                         'term_share_of_52ms_step': round(med['term'] / (STEP_MS * 1e3), 5)})
         print(json.dumps(out), flush=True)
 
