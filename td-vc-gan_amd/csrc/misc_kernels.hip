@@ -316,6 +316,14 @@ __global__ __launch_bounds__(256) void cin_fwd_kernel(const float* x, const floa
   }
 }
 
+// A product rounded on its own, never contracted into a neighbouring add. The three-pass backward forms dh = dy * (1 + gamma)
+// twice: once for the sums, once for dx = rs * (dh - mean(dh) - ...). Contracted into the subtraction, the second dh is the
+// unrounded product while the mean is one of rounded ones: at T = 1, where dx is exactly 0, that left rs * (the rounding of dh).
+__device__ __forceinline__ float cin_mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __global__ __launch_bounds__(256) void cin_bwd_kernel(const float* x, const float* gb, const float* dy, const float* mean,
                                                       const float* rstd, float* dx, float* dgb, int C, int T, int Tg) {
   __shared__ float sh[4];
@@ -328,7 +336,7 @@ __global__ __launch_bounds__(256) void cin_bwd_kernel(const float* x, const floa
   float s1 = 0.f, s2 = 0.f, sg = 0.f, sb = 0.f;
   for (int t = threadIdx.x; t < T; t += 256) {
     const int tg = Tg == 1 ? 0 : t;
-    const float xh = (x[ro + t] - mu) * rs, d = dy[ro + t], dh = d * (1.f + ga[tg]);
+    const float xh = (x[ro + t] - mu) * rs, d = dy[ro + t], dh = cin_mul_rounded(d, 1.f + ga[tg]);
     s1 += dh; s2 += dh * xh;
     if (Tg == 1) { sg += d * xh; sb += d; } else { dga[t] = d * xh; dbe[t] = d; }
   }
@@ -339,7 +347,7 @@ __global__ __launch_bounds__(256) void cin_bwd_kernel(const float* x, const floa
   }
   for (int t = threadIdx.x; t < T; t += 256) {
     const int tg = Tg == 1 ? 0 : t;
-    const float xh = (x[ro + t] - mu) * rs, dh = dy[ro + t] * (1.f + ga[tg]);
+    const float xh = (x[ro + t] - mu) * rs, dh = cin_mul_rounded(dy[ro + t], 1.f + ga[tg]);
     dx[ro + t] = rs * (dh - m1 - xh * m2);
   }
 }
@@ -962,18 +970,18 @@ extern "C" int tdvc_fill(float* y, float value, int64_t n, void* stream) {
 extern "C" int tdvc_cin_fwd(const float* x, const float* gb, float* y, float* mean, float* rstd, int B, int C, int T, int Tg, float eps, void* stream) {
   if (Tg != 1 && Tg != T) return tdvc_fail(TDVC_EINVAL, "cin_fwd: Tg must be 1 or T");
   const bool al = (T & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)gb)) & 15) == 0;
-  if (al && T <= 4096) hipLaunchKernelGGL(cin_fwd_row_kernel<4>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps);
-  else if (al && T <= 16384) hipLaunchKernelGGL(cin_fwd_row_kernel<16>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps);
-  else hipLaunchKernelGGL(cin_fwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps);
+  if (al && T <= 4096) { TDVC_TRACE(cin_fwd_row_kernel<4>); hipLaunchKernelGGL(cin_fwd_row_kernel<4>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps); }
+  else if (al && T <= 16384) { TDVC_TRACE(cin_fwd_row_kernel<16>); hipLaunchKernelGGL(cin_fwd_row_kernel<16>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps); }
+  else { TDVC_TRACE(cin_fwd_kernel); hipLaunchKernelGGL(cin_fwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, y, mean, rstd, C, T, Tg, eps); }
   TDVC_CHECK_LAUNCH(); return TDVC_OK;
 }
 extern "C" int tdvc_cin_bwd(const float* x, const float* gb, const float* dy, const float* mean, const float* rstd,
                             float* dx, float* dgb, int B, int C, int T, int Tg, void* stream) {
   if (Tg != 1 && Tg != T) return tdvc_fail(TDVC_EINVAL, "cin_bwd: Tg must be 1 or T");
   const bool al = (T & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx) | ((uintptr_t)gb) | ((uintptr_t)dgb)) & 15) == 0;
-  if (al && T <= 4096) hipLaunchKernelGGL(cin_bwd_row_kernel<4>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg);
-  else if (al && T <= 8192) hipLaunchKernelGGL(cin_bwd_row_kernel<8>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg);
-  else hipLaunchKernelGGL(cin_bwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg);
+  if (al && T <= 4096) { TDVC_TRACE(cin_bwd_row_kernel<4>); hipLaunchKernelGGL(cin_bwd_row_kernel<4>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg); }
+  else if (al && T <= 8192) { TDVC_TRACE(cin_bwd_row_kernel<8>); hipLaunchKernelGGL(cin_bwd_row_kernel<8>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg); }
+  else { TDVC_TRACE(cin_bwd_kernel); hipLaunchKernelGGL(cin_bwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, gb, dy, mean, rstd, dx, dgb, C, T, Tg); }
   TDVC_CHECK_LAUNCH(); return TDVC_OK;
 }
 
