@@ -509,7 +509,35 @@ int tdvc_segment(const float* x, int64_t x_bs, const int32_t* n, int32_t B, int3
  * (float64 + int32 [B][M]) and, with a path, 2-bit directions [B][N][ceil(M/16)] uint32; the query returns 0 on arguments the
  * call refuses. TDVC_EINVAL for B < 0, non-positive N, M or D, an unknown metric, frame strides < D, negative strides,
  * overlapping path rows, null x, y, cost or length; TDVC_EUNSUPPORTED for N or M > 4096 or D > 64; TDVC_EWORKSPACE for a null or
- * too small workspace; all before any launch. B == 0 is a no-op. */
+ * too small workspace; all before any launch. B == 0 is a no-op.
+ *
+ * tdvc_fastdtw (csrc/eval_fastdtw.hip): FastDTW (S. Salvador, P. Chan, "Toward accurate dynamic time warping in linear time and
+ * space", Intelligent Data Analysis 11, 2007) in the form of the `fastdtw` Python package, the call the reference's test_mcd.py
+ * makes: the same algorithm, NOT the exact programme, so its cost is >= tdvc_dtw's. **Parity with an installed fastdtw package has
+ * NOT been checked** (the package is not available to this repository); what the tests pin is the definition below, restated
+ * literally in tests/fastdtw_ref.py. Arguments, layouts, lengths, metrics, distances (fp32 from direct differences, at every
+ * level), float64 costs and the tie rule are tdvc_dtw's. For one pair x [n][D], y [m][D] and radius r >= 1:
+ *   recursion   if n < r + 2 or m < r + 2: the full programme of tdvc_dtw at this level. Otherwise halve both sequences, solve the
+ *               halved pair, build a window from its path and solve the programme restricted to that window.
+ *   halving     x'[i] = fp32(0.5f * (x[2i] + x[2i+1])) for i < floor(n / 2); an odd last frame is dropped. The pyramid is fp32, one
+ *               rounding per level; the package averages in float64. This is a stated deviation.
+ *   window      every cell within Chebyshev distance r of a cell of the coarse path (cells outside the coarse grid included), each
+ *               coarse cell (a, b) mapped to the fine cells (2a..2a+1, 2b..2b+1) and clipped to the fine grid; the package then
+ *               scans each fine row from the previous row's first column and keeps the first contiguous run. In closed form, with
+ *               n_c coarse rows and jmin(a) / jmax(a) the first / last column of the coarse path in row a, fine row i (c = i / 2)
+ *               gets the columns [max(2 (jmin(max(c - r, 0)) - r), 0), min(2 (jmax(min(c + r, n_c - 1)) + r) + 1, m - 1)].
+ *               The odd last fine row has c = n_c and is covered by the radius alone: hence r >= 1.
+ *   programme   C(i,j) = d(i,j) + min(C(i-1,j), C(i,j-1), C(i-1,j-1)) over the cells of the window, +inf outside, C(0,0) = d(0,0),
+ *               the FIRST minimum in the order up, left, diagonal (the package's tuple order); the path is traced back from
+ *               (n-1, m-1) along the chosen predecessors.
+ * cost[b] = C(n-1, m-1) at the finest level, length[b] = the cells of its path, path as for tdvc_dtw. A pair with n[b] == 0 or
+ * m[b] == 0 gets cost NaN, length 0 and a path row of -1. One launch, one block per pair, the whole pyramid inside it; no atomics,
+ * no allocation, no synchronisation: graph-capturable, bit-identical from call to call. The work is O((n + m) r) cells, a window
+ * holding at most (4 r + 2) (n + m - 1). The workspace holds the fp32 pyramids, the window's row bounds and 16 bytes of directions
+ * per anti-diagonal; tdvc_fastdtw_workspace is an upper bound for any lengths up to N, M (want_path does not change it) and
+ * returns 0 on arguments the call refuses. TDVC_EINVAL for B < 0, non-positive N, M or D, an unknown metric, radius < 1, frame
+ * strides < D, negative strides, path_bs < 2 (N + M - 1) with a path, null x, y, cost or length; TDVC_EUNSUPPORTED for N or
+ * M > 16384, D > 64 or radius > 8; TDVC_EWORKSPACE for a null or too small workspace; all before any launch. B == 0 is a no-op. */
 enum { TDVC_DTW_L2 = 0, TDVC_DTW_L1 = 1, TDVC_DTW_SQ = 2 };
 int tdvc_sp2mc(const float* power, int64_t p_bs, int64_t p_fs, int64_t p_ns, const double* mat, int32_t B, int32_t F, int32_t nbins,
                int32_t order, float floor_, float* mc, void* stream);
@@ -517,6 +545,10 @@ size_t tdvc_dtw_workspace(int32_t B, int32_t N, int32_t M, int32_t want_path);
 int tdvc_dtw(const float* x, int64_t x_bs, int64_t x_fs, const float* y, int64_t y_bs, int64_t y_fs, const int32_t* n, const int32_t* m,
              int32_t B, int32_t N, int32_t M, int32_t D, int32_t metric, double* cost, int32_t* length, int32_t* path, int64_t path_bs,
              void* workspace, size_t workspace_bytes, void* stream);
+size_t tdvc_fastdtw_workspace(int32_t B, int32_t N, int32_t M, int32_t D, int32_t radius, int32_t want_path);
+int tdvc_fastdtw(const float* x, int64_t x_bs, int64_t x_fs, const float* y, int64_t y_bs, int64_t y_fs, const int32_t* n, const int32_t* m,
+                 int32_t B, int32_t N, int32_t M, int32_t D, int32_t metric, int32_t radius, double* cost, int32_t* length, int32_t* path,
+                 int64_t path_bs, void* workspace, size_t workspace_bytes, void* stream);
 
 /* tdvc_cheaptrick (csrc/eval_cheaptrick.hip): WORLD's CheapTrick spectral envelope (M. Morise, "CheapTrick, a spectral envelope
  * estimator for high-quality speech synthesis", Speech Communication 67, 2015; WORLD's cheaptrick.cpp / common.cpp), the

@@ -7,7 +7,7 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     inference scripts), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
     EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
     load_audio's resampling and segment preparation as resample / load_segments (resample.py), and the objective evaluation of
-    test_scripts/common/test_mcd.py as mcd / dtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats, with WORLD's CheapTrick envelope as cheaptrick (evaluate.py).
+    test_scripts/common/test_mcd.py as mcd / dtw / fastdtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats, with WORLD's CheapTrick envelope as cheaptrick (evaluate.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -32,7 +32,7 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.corrupt'), name)
     if name in ('resample_filter', 'resample_bank', 'load_segments'):      # `resample` is the (callable) module itself, above
         return getattr(importlib.import_module(f'{__name__}.resample'), name)
-    if name in ('dtw', 'mcd', 'f0_stats', 'sp2mc', 'sp2mc_matrix', 'mel_cepstrum', 'cheaptrick', 'cheaptrick_mc_matrix'):
+    if name in ('dtw', 'fastdtw', 'mcd','f0_stats', 'sp2mc', 'sp2mc_matrix', 'mel_cepstrum', 'cheaptrick', 'cheaptrick_mc_matrix'):
         return getattr(importlib.import_module(f'{__name__}.evaluate'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)

@@ -182,6 +182,9 @@ SIGNATURES = {
     'tdvc_dtw_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_dtw': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64,
                       _vp, C.c_size_t, _vp]),
+    'tdvc_fastdtw_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_fastdtw': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp,
+                          _vp, _i64, _vp, C.c_size_t, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

@@ -6,14 +6,18 @@
                                                          opt-in (envelope='cheaptrick' in `mel_cepstrum` / `mcd`, which then take the mel-cepstrum
                                                          from the same launch); the default stays a plain Hann STFT power spectrum
     pysptk.sp2mc(sp, 24, 0.42)                           sp2mc: tdvc_sp2mc (csrc/eval_mcep.hip), the definition in include/tdvc.h
-    fastdtw(test, ref, dist=2) -> dist / len(path)       dtw: tdvc_dtw (csrc/eval_dtw.hip), the EXACT programme
+    fastdtw(test, ref, dist=2) -> dist / len(path)       fastdtw: tdvc_fastdtw (csrc/eval_fastdtw.hip), the same algorithm, opt-in in `mcd`
+                                                         (align='fastdtw'); the default stays dtw: tdvc_dtw (csrc/eval_dtw.hip), the EXACT programme
 
 Three parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: **parity of
 `cheaptrick` with pyworld is still unchecked** (it follows WORLD's cheaptrick.cpp as restated in include/tdvc.h, with two stated
 deviations: a deterministic floor, S = max(S, floor) + 2.2e-16, where WORLD adds noise from its own generator, so frames of digital
 silence differ; and an F0 above fs/4 counts as unvoiced, where WORLD has no cap and reads out of range), `sp2mc` is believed to be
-pysptk's, and `dtw` is exact where fastdtw is an approximation with radius 1, so the cost here is a lower bound on fastdtw's (the
-tie order up, left, diagonal is believed to be fastdtw's tuple order).
+pysptk's, and `dtw` is exact where fastdtw is an approximation with radius 1, so its cost is a lower bound on fastdtw's (the
+tie order up, left, diagonal is believed to be fastdtw's tuple order). The alignment of the reference is now available as the
+same algorithm: `fastdtw` restates the package (recursion, halving, window expansion, windowed programme; include/tdvc.h), but
+**parity with the installed fastdtw package is still unchecked**, its pyramid of halved sequences is fp32 where the package
+averages in float64 (a stated deviation: one fp32 rounding per level), and the radius is limited to 1..8.
 
 Nothing here synchronises with the host: lengths and voicing stay on the device, the voiced frames are compacted by a prefix
 sum and a scatter, and the per-pair lengths go into the kernel as device int32.
@@ -31,6 +35,7 @@ from .ops import ConvSpec
 
 METRICS = {'l2': L.DTW_L2, 'l1': L.DTW_L1, 'sq': L.DTW_SQ}
 DTW_MAX_LEN, DTW_MAX_D = 4096, 64      # csrc/eval_dtw.hip
+FASTDTW_MAX_LEN, FASTDTW_MAX_RADIUS = 16384, 8      # csrc/eval_fastdtw.hip
 POWER_FLOOR = 1e-10                    # default floor under the logarithm: -100 dB against a full-scale bin of power 1
 # default floor under CheapTrick's smoothed spectrum. Its window has sum w^2 = 1, so white noise of variance v gives P = v per bin: 1e-16
 # is the rounding noise of an fp32 waveform at full scale (2^-48 / 12 = 3e-16), below which nothing in an fp32 signal is information,
@@ -38,6 +43,7 @@ POWER_FLOOR = 1e-10                    # default floor under the logarithm: -100
 CHEAPTRICK_FLOOR = 1e-16
 CHEAPTRICK_N_FFT = (512, 1024, 2048)   # the compiled instances of csrc/eval_cheaptrick.hip
 ENVELOPES = ('stft', 'cheaptrick')
+ALIGNMENTS = ('exact', 'fastdtw')
 
 _stft_cache = {}
 
@@ -261,6 +267,45 @@ def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
     return (cost, length, path.long()) if return_path else (cost, length)
 
 
+def fastdtw(x, y, x_len=None, y_len=None, radius=1, metric='l2', return_path=False):
+    """FastDTW of x [B, N, D] against y [B, M, D] (device fp32; [N, D] / [M, D] for one pair) -> (cost float64 [B], length int32 [B]
+    [, path int64 [B, N + M - 1, 2]]): the reference's fastdtw(x, y, radius=1, dist=2) as the same algorithm; tdvc_fastdtw, one
+    launch with the whole pyramid inside it, no host synchronisation. Layouts, strides, lengths, metrics, tie rule and return
+    values are exactly `dtw`'s; the definition (recursion, halving, window) is written out in include/tdvc.h. The cost is an
+    approximation from above of `dtw`'s exact optimum, in O((N + M) radius) work.
+    **Parity with the installed fastdtw package is unchecked**, and the pyramid of halved sequences is fp32 (one rounding per
+    level) where the package averages in float64. N, M <= 16384, D <= 64, 1 <= radius <= 8."""
+    H.need_device('fastdtw', x, y)
+    if metric not in METRICS:
+        raise ValueError(f'fastdtw: unknown metric {metric!r} (known: {sorted(METRICS)})')
+    if x.dim() != y.dim() or x.dim() not in (2, 3):
+        raise ValueError('fastdtw: x and y must both be [N, D] or both [B, N, D]')
+    radius = int(radius)
+    if radius < 1:
+        raise ValueError('fastdtw: the radius must be at least 1')
+    single = x.dim() == 2
+    x3, x_bs, x_fs = H.frames3('fastdtw', x)
+    y3, y_bs, y_fs = H.frames3('fastdtw', y)
+    B, N, D = x3.shape
+    if y3.shape[0] != B or y3.shape[2] != D:
+        raise ValueError(f'fastdtw: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in batch or feature size')
+    M = y3.shape[1]
+    dev = x3.device
+    xl, yl = _len_arg('fastdtw', x_len, B, dev), _len_arg('fastdtw', y_len, B, dev)
+    lib = L.lib()
+    cost = torch.empty(B, dtype=torch.float64, device=dev)
+    length = torch.empty(B, dtype=torch.int32, device=dev)
+    P = N + M - 1
+    path = torch.full((B, max(P, 0), 2), -1, dtype=torch.int32, device=dev) if return_path else None
+    nbytes = lib.tdvc_fastdtw_workspace(B, N, M, D, radius, int(return_path)) if B > 0 else 0
+    ws = H.scratch(nbytes, dev)
+    L.check(lib.tdvc_fastdtw(x3.data_ptr(), x_bs, x_fs, y3.data_ptr(), y_bs, y_fs, H.ptr(xl), H.ptr(yl), B, N, M, D, METRICS[metric], radius,
+                             cost.data_ptr(), length.data_ptr(), H.ptr(path), 2 * P, ws.data_ptr(), nbytes, H.stream(x3)))
+    if single:
+        cost, length, path = cost[0], length[0], (path[0] if return_path else None)
+    return (cost, length, path.long()) if return_path else (cost, length)
+
+
 # ------------------------------------------------------------------------------------------------------------ MCD
 def f0_stats(f0_test, f0_ref):
     """The F0 statistics of test_mcd.py:83-84 and :116 from two tracks [..., F] in Hz (0 = unvoiced; the two may differ in F) ->
@@ -322,7 +367,7 @@ def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, m
 
 
 def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None, f0_ref=None, drop_c0=False, db=False, min_voiced=10,
-        envelope='stft', **mel_kwargs):
+        envelope='stft', align='exact', radius=1, **mel_kwargs):
     """Mel-cepstral distortion of test [B, 1, T1] against ref [B, 1, T2] (device waveforms; *_len: valid samples per row as device
     integers [B]) -> dict of device tensors [B]: the counterpart of test_mcd.py's mfcc_dist + f0_ratio.
 
@@ -334,7 +379,9 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
     Frame alignment: STFT frame f and YIN frame f are both centred on sample f * hop (the STFT reflects n_fft/2 samples, YIN
     zero-pads half a frame), so frame f of one is frame f of the other; the STFT has one frame more when T is a multiple of
     hop, and the common frames are kept. With a length, the frames centred inside the row, f * hop < length, count.
-    The voiced frames of each side are compacted on the device and aligned by `dtw` (metric 'l2').
+    The voiced frames of each side are compacted on the device and aligned with metric 'l2': align='exact' (the default) by `dtw`,
+    the exact programme (at most 4096 frames, 20.5 s); align='fastdtw' by `fastdtw` with `radius`, the reference's alignment as the
+    same algorithm (at most 16384 frames; parity with the installed fastdtw package is unchecked, and its pyramid is fp32 here).
         mcd = cost / path_len      plain Euclidean distance including c0: the reference's number
         drop_c0=True leaves c0 out; db=True multiplies by 10 / ln(10) * sqrt(2): together the conventional MCD in dB
         path_len, n_test, n_ref    cells of the path, voiced frames of each side
@@ -347,12 +394,15 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
             raise ValueError('mcd: waveforms must be [B, 1, T] with one batch size')
     if envelope not in ENVELOPES:
         raise ValueError(f'mcd: unknown envelope {envelope!r} (known: {ENVELOPES})')
+    if align not in ALIGNMENTS:
+        raise ValueError(f'mcd: unknown align {align!r} (known: {ALIGNMENTS})')
     hop = int(round(sample_rate * 0.005))
     a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, envelope, mel_kwargs)
     b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, envelope, mel_kwargs)
-    if a.shape[1] > DTW_MAX_LEN or b.shape[1] > DTW_MAX_LEN:
-        raise ValueError(f'mcd: more than {DTW_MAX_LEN} frames ({DTW_MAX_LEN * 0.005:.1f} s); evaluate shorter segments')
-    cost, length = dtw(a, b, na, nb, metric='l2')
+    max_len = FASTDTW_MAX_LEN if align == 'fastdtw' else DTW_MAX_LEN
+    if a.shape[1] > max_len or b.shape[1] > max_len:
+        raise ValueError(f'mcd: more than {max_len} frames ({max_len * 0.005:.1f} s); evaluate shorter segments')
+    cost, length = fastdtw(a, b, na, nb, radius=radius, metric='l2') if align == 'fastdtw' else dtw(a, b, na, nb, metric='l2')
     ok = (na >= min_voiced) & (nb >= min_voiced)
     nan = torch.full_like(cost, float('nan'))
     scale = 10.0 / math.log(10.0) * math.sqrt(2.0) if db else 1.0
