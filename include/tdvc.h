@@ -590,6 +590,80 @@ int tdvc_cheaptrick(const float* signal, int64_t s_bs, int64_t s_ts, const int32
                     int64_t f0_fs, int32_t B, int32_t F, int32_t hop, int32_t fs, int32_t n_fft, double q1, double floor_,
                     const double* G, int32_t order, float* env, float* mc, void* stream);
 
+/* tdvc_dio, tdvc_stonemask (csrc/pitch_dio.hip): WORLD's DIO F0 estimator and its StoneMask refinement (M. Morise, H. Kawahara,
+ * H. Katayose, "Fast and reliable F0 estimation method based on the period extraction of vocal fold vibration of singing voice and
+ * speech", AES 35th Int. Conf., 2009; WORLD's dio.cpp, stonemask.cpp, matlabfunctions.cpp), the pyworld.dio + pyworld.stonemask step
+ * of the reference's world_analyze with pyworld's defaults speed = 1, channels_in_octave = 2, allowed_range = 0.1. **Parity with
+ * pyworld has NOT been checked** (pyworld is not available to this repository); what the tests pin is the definition below, restated
+ * literally in float64 numpy in tests/dio_ref.py. eps = 1e-12, BIG = 100000, mround(v) = (int)(v + 0.5) for v > 0 and (int)(v - 0.5)
+ * otherwise (matlab_round); len = the row's valid length, lengths[b] clamped to [0, T] (NULL = T). There is no decimation (speed).
+ *
+ * DIO, per row:
+ *   frames      F_b = len / hop + 1 (integer division), t_i = i hop / fs; frames at and past F_b are 0
+ *   bands       nb = 1 + (int)(log2(f0_ceil / f0_floor) cpo), bf[k] = f0_floor 2^((k + 1)/cpo): 7 bands at 50 / 500 / 2
+ *   pre-filter  y = x - mean(x[0 .. len)); c = mround(fs/50); h[i] = 0.5 - 0.5 cos(2 pi (i + 1)/(2c + 2)), i = 0 .. 2c; h = -h / sum(h),
+ *               h[c] += 1; y <- sum_j h[j] y[i + c - j]: a zero-phase low-cut, zeros outside [0, len)
+ *   band filter hal = mround(fs / bf[k] / 2); w = the Nuttall window of 4 hal points, 0.355768 - 0.487396 cos(2 pi u) + 0.144232 cos(4 pi u)
+ *               - 0.012604 cos(6 pi u), u = j/(4 hal - 1); f[i] = sum_j w[j] y[i + 2 hal - j], i = 0 .. len - 1, zeros outside [0, len).
+ *               Stated deviation (both filters): WORLD multiplies the spectra of one zero-padded FFT, a circular convolution that
+ *               wraps into the first few hundred samples when the padding happens to be tight; here both are linear.
+ *   events      four lists from the sequences f, -f, -(f[i+1] - f[i]) and f[i+1] - f[i] (negative- and positive-going crossings, peaks,
+ *               dips): on a sequence g every i with 0 < g[i] and g[i+1] <= 0 gives fine = (i + 1) - g[i]/(g[i+1] - g[i]) (the + 1
+ *               is WORLD's); consecutive fines a < b give an interval at (a + b)/2/fs of value fs/(b - a)
+ *   candidate   if any list has <= 2 intervals the band has cand = 0, score = BIG/eps in every frame. Otherwise each list is
+ *               interpolated linearly at t_i, extrapolated from the first segment below the first location and from the last one
+ *               at and above the last location (histc + interp1: with k = the number of locations <= t_i clipped to
+ *               [1, n - 1], the line through intervals k - 1 and k); cand = (((v0 + v1) + v2) + v3)/4, score = sqrt(sum (v - cand)^2/3);
+ *               cand > bf[k], cand < bf[k]/2, cand > f0_ceil or cand < f0_floor give cand = 0, score = BIG; last score /= cand + eps
+ *   best        per frame the candidate of the lowest score, the lowest band on a tie
+ *   fix         vrm = (int)(0.5 + fs/hop/f0_floor) 2 + 1, c = (vrm - 1)/2; F_b <= vrm: every frame is 0 (WORLD leaves the array unset).
+ *               step 1  base = best with the first and last vrm frames 0; s1[i] = base[i] if |(base[i] - base[i-1])/(eps + base[i])| <
+ *                       allowed else 0, for i >= vrm (0 below)
+ *               step 2  s2 = s1, and s2[i] = 0 where any of s1[i - c .. i + c] is 0, for c <= i < F_b - c
+ *               ends    neg = every i - 1 with s2[i] == 0 != s2[i-1], pos = every i with s2[i-1] == 0 != s2[i], ascending
+ *               step 3  s3 = s2; from each neg[n], j runs up to the next neg (F_b - 1 after the last), exclusive:
+ *                       s3[j+1] = select(s3[j], s3[j-1], j + 1), and the run stops at the first 0
+ *               step 4  s4 = s3; from each pos, last first, j runs down to the previous pos (1 before the first), exclusive:
+ *                       s4[j-1] = select(s4[j], s4[j+1], j - 1), and the run stops at the first 0
+ *               select(cur, past, t): ref = (3 cur - past)/2; v = the candidate of frame t nearest to ref over the bands (the lowest
+ *                       band on a tie); 0 if |1 - v/ref| > allowed, else v
+ *               f0 = s4, rounded once to fp32.
+ * StoneMask, per frame fr with f = f0_in[b][fr] (fp32): f not finite, f <= 40 or f > fs/12 (or len == 0) gives 0. Otherwise
+ *   t = fr hop / fs, half = (int)(1.5 fs/f + 1), N = 2^(2 + floor(log2(2 half + 1))); for k = -half .. half
+ *   raw_k = mround((t + k/fs) fs + 0.001), sample x[clamp(raw_k - 1, 0, len - 1)], u_k = ((raw_k - 1)/fs - t)/((2 half + 1)/fs),
+ *   mw = 0.42 + 0.5 cos(2 pi u) + 0.08 cos(4 pi u), dw[k] = -(mw[k+1] - mw[k-1])/2 with mw = 0 beyond both ends;
+ *   M = DFT_N(x mw), D = DFT_N(x dw) from offset 0, P = |M|^2, num = Re M Im D - Im M Re D.
+ *   fix(g, nh) = sum_h amp_h IF_h / (sum_h amp_h h + eps) over h = 1 .. nh with idx = mround(g N / fs h), amp = sqrt(P[idx]),
+ *   IF = idx fs/N + num[idx]/P[idx] fs/2/pi (0 where P = 0); the bins are read modulo N (idx can reach N; WORLD reads out of range).
+ *   tent = fix(f, 2); r = 0 if tent <= 0 or tent > 2 f, else fix(tent, min((int)(fs/2/f), 6)); |r - f| > 0.2 f gives r = f.
+ *   Only the at most 8 bins named by idx are evaluated, by direct summation with the phase (idx n) mod N reduced in integers.
+ *   Stated deviation: the input track is fp32, so stonemask(dio(x)) passes DIO's result through one fp32 rounding where WORLD
+ *   keeps float64.
+ * signal fp32 at signal[b * s_bs + t * s_ts], samples at and past len never read. tdvc_dio: f0 fp32 [B][F], rows f0_bs >= F apart,
+ * F >= T / hop + 1 (every frame of a full row; columns at and past F are not touched); cand / score, each NULL or float64
+ * [B][nb][F] dense: the per-band candidates and scores (0 and BIG/eps at and past F_b). tdvc_stonemask: f0_in at
+ * f0_in[b * fi_bs + fr * fi_fs], f0_out fp32 rows fo_bs >= F apart; f0_out may be f0_in. Float64 arithmetic, one rounding at the
+ * store; no atomics, fixed summation orders: bit-identical from call to call; no allocation, no synchronisation, graph-capturable.
+ * tdvc_dio is 7 launches (tables, row mean, low-cut, the band filter twice: counting the events per 1022-sample tile, then
+ * writing them behind the tiles before; candidates; one wave per row for the fix steps), tdvc_stonemask one, a block per frame.
+ * The workspace holds y (8 T bytes per row), the events (512 slots per tile, kind and band: 16 nb T bytes per row, the bulk), the
+ * candidates and scores; tdvc_dio_workspace returns 0 on arguments the call refuses and for B == 0. tdvc_dio_num_bands returns
+ * nb, 0 when the call would refuse it.
+ * TDVC_EINVAL: negative B, T, F or strides, hop or fs < 1, not 0 < f0_floor < f0_ceil finite, channels_in_octave or allowed_range not
+ * positive and finite, a band at or above fs, F < T / hop + 1, overlapping output rows, null signal (with T > 0) or f0. TDVC_EUNSUPPORTED:
+ * nb > 16, T > 2^21 (131 s at 16 kHz), B > 65535, a low-cut (2 mround(fs/50) + 1) or lowest-band (4 hal) filter of more than 2048 taps
+ * (fs <= 51 kHz; fs / f0_floor <= 1449 at 2 channels per octave), fs/hop/f0_floor > 10^6; for tdvc_stonemask a 40 Hz window
+ * (2 (int)(1.5 fs/40 + 1) + 1) of more than 4096 samples (fs <= 54 kHz), more than 2^31 - 1 frames or samples. TDVC_EWORKSPACE for a
+ * null or too small workspace. All before any launch. B == 0 or F == 0 is a no-op. */
+int32_t tdvc_dio_num_bands(double f0_floor, double f0_ceil, double channels_in_octave);
+size_t tdvc_dio_workspace(int32_t B, int32_t T, int32_t F, int32_t hop, int32_t fs, double f0_floor, double f0_ceil,
+                          double channels_in_octave);
+int tdvc_dio(const float* signal, int64_t s_bs, int64_t s_ts, const int32_t* lengths, int32_t T, int32_t B, int32_t F, int32_t hop,
+             int32_t fs, double f0_floor, double f0_ceil, double channels_in_octave, double allowed_range, float* f0, int64_t f0_bs,
+             double* cand, double* score, void* workspace, size_t workspace_bytes, void* stream);
+int tdvc_stonemask(const float* signal, int64_t s_bs, int64_t s_ts, const int32_t* lengths, int32_t T, const float* f0_in, int64_t fi_bs,
+                   int64_t fi_fs, int32_t B, int32_t F, int32_t hop, int32_t fs, float* f0_out, int64_t fo_bs, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

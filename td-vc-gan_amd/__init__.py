@@ -7,7 +7,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     inference scripts), and the data pipeline's signal corruption (data/dataset.py corrupt_audio: a random parametric
     EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
     load_audio's resampling and segment preparation as resample / load_segments (resample.py), and the objective evaluation of
-    test_scripts/common/test_mcd.py as mcd / dtw / fastdtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats, with WORLD's CheapTrick envelope as cheaptrick (evaluate.py).
+    test_scripts/common/test_mcd.py as mcd / dtw / fastdtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats, with WORLD's CheapTrick envelope as cheaptrick (evaluate.py)
+    and WORLD's DIO + StoneMask F0 as dio / stonemask / world_f0 (pitch.py; mcd(f0_method='dio')).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -26,7 +27,7 @@ def __getattr__(name):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
-    if name in ('yin_f0', 'track_f0', 'viterbi_transition', 'viterbi_path'):
+    if name in ('yin_f0', 'track_f0', 'viterbi_transition', 'viterbi_path', 'dio', 'stonemask', 'world_f0'):
         return getattr(importlib.import_module(f'{__name__}.pitch'), name)
     if name in ('peq_sos', 'sos_filter', 'random_eq', 'corrupt_audio', 'device_batch'):
         return getattr(importlib.import_module(f'{__name__}.corrupt'), name)

@@ -167,6 +167,11 @@ SIGNATURES = {
     'tdvc_yin_soft_bwd': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _vp, _vp, _vp, C.c_size_t, _vp]),
     'tdvc_viterbi_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_viterbi_path': (_i, [_vp, _i64, _i64, _f, _vp, _vp, _vp, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp, C.c_size_t, _vp]),
+    'tdvc_dio_num_bands': (C.c_int32, [C.c_double, C.c_double, C.c_double]),
+    'tdvc_dio_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    'tdvc_dio': (_i, [_vp, _i64, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                      _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    'tdvc_stonemask': (_i, [_vp, _i64, _i64, _vp, C.c_int32, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
     'tdvc_peq_sos': (_i, [_vp, _vp, _vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp]),
     'tdvc_sos_filter_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_sos_filter': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp, C.c_size_t, _vp]),

@@ -1,7 +1,9 @@
 """Objective evaluation on the device: the reference's test_scripts/common/test_mcd.py (mfcc_dist + f0_ratio) as library calls.
 
     reference                                            here
-    pyworld.dio / stonemask (F0, voicing)                pitch.yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005), or the caller's tracks
+    pyworld.dio / stonemask (F0, voicing)                pitch.world_f0: tdvc_dio + tdvc_stonemask (csrc/pitch_dio.hip), the definition in
+                                                         include/tdvc.h; opt-in (f0_method='dio' in `mcd`); the default stays
+                                                         pitch.yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005); or the caller's tracks
     pyworld.cheaptrick (spectral envelope)               cheaptrick: tdvc_cheaptrick (csrc/eval_cheaptrick.hip), the definition in include/tdvc.h;
                                                          opt-in (envelope='cheaptrick' in `mel_cepstrum` / `mcd`, which then take the mel-cepstrum
                                                          from the same launch); the default stays a plain Hann STFT power spectrum
@@ -9,7 +11,12 @@
     fastdtw(test, ref, dist=2) -> dist / len(path)       fastdtw: tdvc_fastdtw (csrc/eval_fastdtw.hip), the same algorithm, opt-in in `mcd`
                                                          (align='fastdtw'); the default stays dtw: tdvc_dtw (csrc/eval_dtw.hip), the EXACT programme
 
-Three parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: **parity of
+With f0_method='dio', envelope='cheaptrick' and align='fastdtw', `mcd` runs the reference's whole pipeline as the same algorithms.
+Four parities are NOT checked, because none of pyworld, pysptk and fastdtw is available to this repository: **parity of `dio` and
+`stonemask` with pyworld is unchecked** (they follow WORLD's dio.cpp, stonemask.cpp and matlabfunctions.cpp with pyworld's defaults
+as restated in include/tdvc.h, with two stated deviations: the low-cut and the band filters are linear convolutions where WORLD
+multiplies the spectra of one zero-padded FFT, which wraps into the first few hundred samples when the padding is tight; and
+StoneMask reads DIO's track after one fp32 rounding where WORLD keeps float64), **parity of
 `cheaptrick` with pyworld is still unchecked** (it follows WORLD's cheaptrick.cpp as restated in include/tdvc.h, with two stated
 deviations: a deterministic floor, S = max(S, floor) + 2.2e-16, where WORLD adds noise from its own generator, so frames of digital
 silence differ; and an F0 above fs/4 counts as unvoiced, where WORLD has no cap and reads out of range), `sp2mc` is believed to be
@@ -43,6 +50,7 @@ POWER_FLOOR = 1e-10                    # default floor under the logarithm: -100
 CHEAPTRICK_FLOOR = 1e-16
 CHEAPTRICK_N_FFT = (512, 1024, 2048)   # the compiled instances of csrc/eval_cheaptrick.hip
 ENVELOPES = ('stft', 'cheaptrick')
+F0_METHODS = ('yin', 'dio')
 ALIGNMENTS = ('exact', 'fastdtw')
 
 _stft_cache = {}
@@ -338,7 +346,7 @@ def compact_voiced(mc, voiced):
     return out[:, :F], voiced.sum(1).to(torch.int32)
 
 
-def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, mel_kwargs):
+def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, mel_kwargs, f0_method='yin'):
     """Mel-cepstra of the voiced frames of sig [B, 1, T], compacted, their count, and the F0 track used."""
     B, _, T = sig.shape
     cheap = envelope == 'cheaptrick'
@@ -346,7 +354,10 @@ def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, m
         mc = mel_cepstrum(sig, sample_rate=sample_rate, hop=hop, **mel_kwargs)
     if f0 is None:
         from . import pitch
-        f0 = pitch.yin_f0(sig[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
+        if f0_method == 'dio':
+            f0 = pitch.world_f0(sig[:, 0], sample_rate, hop, 50.0, 500.0, lengths=length)
+        else:
+            f0 = pitch.yin_f0(sig[:, 0], sample_rate, pitch_min=50, pitch_max=500, frame_stride=hop / sample_rate)
     elif f0.dim() != 2 or f0.shape[0] != B:
         raise ValueError(f'{who}: an F0 track must be [B, n_frames]')
     if cheap:                                                                     # one F0 track for the envelope and for the voicing
@@ -367,7 +378,7 @@ def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, m
 
 
 def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None, f0_ref=None, drop_c0=False, db=False, min_voiced=10,
-        envelope='stft', align='exact', radius=1, **mel_kwargs):
+        envelope='stft', align='exact', radius=1, f0_method='yin', **mel_kwargs):
     """Mel-cepstral distortion of test [B, 1, T1] against ref [B, 1, T2] (device waveforms; *_len: valid samples per row as device
     integers [B]) -> dict of device tensors [B]: the counterpart of test_mcd.py's mfcc_dist + f0_ratio.
 
@@ -376,6 +387,9 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
     reference does: the F0 track is obtained first and serves both the envelope and the voicing, frame f of the cepstra IS frame f
     of the track, and samples at and past a length are never read.
     Voicing from yin_f0(pitch_min=50, pitch_max=500, frame_stride=0.005) or from the caller's f0_test / f0_ref [B, n_frames].
+    f0_method='dio' takes it from pitch.world_f0(f0_floor=50, f0_ceil=500) instead: WORLD's DIO refined by StoneMask, as the reference
+    does (samples at and past a length are never read; parity with pyworld is unchecked). With envelope='cheaptrick' and
+    align='fastdtw' the call is then the reference's pipeline, step for step, as the same algorithms.
     Frame alignment: STFT frame f and YIN frame f are both centred on sample f * hop (the STFT reflects n_fft/2 samples, YIN
     zero-pads half a frame), so frame f of one is frame f of the other; the STFT has one frame more when T is a multiple of
     hop, and the common frames are kept. With a length, the frames centred inside the row, f * hop < length, count.
@@ -396,9 +410,11 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
         raise ValueError(f'mcd: unknown envelope {envelope!r} (known: {ENVELOPES})')
     if align not in ALIGNMENTS:
         raise ValueError(f'mcd: unknown align {align!r} (known: {ALIGNMENTS})')
+    if f0_method not in F0_METHODS:
+        raise ValueError(f'mcd: unknown f0_method {f0_method!r} (known: {F0_METHODS})')
     hop = int(round(sample_rate * 0.005))
-    a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, envelope, mel_kwargs)
-    b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, envelope, mel_kwargs)
+    a, na, f0a = _voiced_cepstra('mcd', test.detach().float(), test_len, f0_test, sample_rate, hop, drop_c0, envelope, mel_kwargs, f0_method)
+    b, nb, f0b = _voiced_cepstra('mcd', ref.detach().float(), ref_len, f0_ref, sample_rate, hop, drop_c0, envelope, mel_kwargs, f0_method)
     max_len = FASTDTW_MAX_LEN if align == 'fastdtw' else DTW_MAX_LEN
     if a.shape[1] > max_len or b.shape[1] > max_len:
         raise ValueError(f'mcd: more than {max_len} frames ({max_len * 0.005:.1f} s); evaluate shorter segments')

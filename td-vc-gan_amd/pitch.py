@@ -14,6 +14,10 @@ util.crepe.filtered_pitch(signal, "viterbi") (generate_with_target.py:139), whos
 with a triangular +-240 cent transition. Here the lattice is the CMDF the YIN launch already produces, decoded by
 tdvc_viterbi_path (csrc/pitch_viterbi.hip); `viterbi_transition` builds the band table and `viterbi_path` is the raw decoder for a
 caller with a lattice of its own (CREPE activations included).
+
+`dio`, `stonemask` and `world_f0` are WORLD's F0 estimator and its refinement, the pyworld.dio + pyworld.stonemask step of the
+reference's objective evaluation (test_scripts/common/test_mcd.py world_analyze), as HIP kernels in float64 (csrc/pitch_dio.hip,
+tdvc_dio / tdvc_stonemask; the definition is written out in include/tdvc.h). Parity with pyworld is unchecked.
 """
 import math
 import weakref
@@ -226,3 +230,75 @@ def track_f0(signal, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, thr
         f0 = _yin(signal[:, 0], sample_rate, tau_min, tau_max, int(hop), threshold, soft, False)
     idx = torch.arange(T // int(hop) + 1, device=f0.device).clamp_(max=f0.shape[-1] - 1)
     return f0.index_select(-1, idx).unsqueeze(1)
+
+
+# ------------------------------------------------------------------------------------------------------------ WORLD's DIO + StoneMask
+def _world_rows(who, signal, lengths):
+    H.need_device(who, signal)
+    x2, x_bs, lead = H.rows2(who, signal)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths, device=x2.device) if not torch.is_tensor(lengths) else lengths.to(x2.device)
+        if lengths.numel() != x2.shape[0]:
+            raise ValueError(f'{who}: lengths must hold one entry per row ({x2.shape[0]})')
+        lengths = lengths.reshape(-1).to(torch.int32).contiguous()
+    return x2, x_bs, lead, lengths
+
+
+def dio(signal, sample_rate=16000, hop=80, f0_floor=50.0, f0_ceil=500.0, channels_in_octave=2.0, allowed_range=0.1, lengths=None,
+        return_candidates=False):
+    """WORLD's DIO F0 track of signal [T], [B, T] or [B, 1, T] (device fp32, last axis dense) -> fp32 [..., T // hop + 1] in Hz, 0 =
+    unvoiced: the counterpart of pyworld.dio(x, fs, f0_floor, f0_ceil, channels_in_octave, frame_period = 1000 hop / fs,
+    allowed_range) without decimation (speed = 1); tdvc_dio (csrc/pitch_dio.hip), the definition in include/tdvc.h. Frame i is at
+    sample i * hop. lengths: device integers, valid samples per row; samples at and past them are never read, and frames past
+    lengths[b] // hop are 0. Rows of a wider buffer go in as views. return_candidates=True also returns the per-band candidates and
+    scores, float64 [..., n_bands, T // hop + 1] each. Float64 arithmetic, seven launches, no host synchronisation.
+    **Parity with pyworld is unchecked**; both band-limiting filters are linear convolutions where WORLD's FFT product is circular.
+    At most 16 bands, 2^21 samples per row, filters of 2048 taps (any fs up to 51 kHz with f0_floor >= fs / 1449)."""
+    x2, x_bs, lead, ln = _world_rows('dio', signal, lengths)
+    B, T = x2.shape
+    hop, fs = int(hop), int(sample_rate)
+    if hop < 1 or fs != sample_rate:
+        raise ValueError('dio: needs an integer sample rate and hop >= 1')
+    par = (float(f0_floor), float(f0_ceil), float(channels_in_octave))
+    lib = L.lib()
+    F = T // hop + 1
+    nb = lib.tdvc_dio_num_bands(*par)
+    f0 = torch.empty(B, F, dtype=torch.float32, device=x2.device)
+    cand = torch.empty(B, max(nb, 0), F, dtype=torch.float64, device=x2.device) if return_candidates else None
+    score = torch.empty_like(cand) if return_candidates else None
+    nbytes = lib.tdvc_dio_workspace(B, T, F, hop, fs, *par)
+    ws = H.scratch(nbytes, x2.device)
+    H.check('dio', lib.tdvc_dio(x2.data_ptr(), x_bs, 1, H.ptr(ln), T, B, F, hop, fs, *par, float(allowed_range), f0.data_ptr(), F, H.ptr(cand),
+                                H.ptr(score), ws.data_ptr(), nbytes, H.stream(x2)))
+    f0 = f0.reshape(*lead, F)
+    return (f0, cand.reshape(*lead, nb, F), score.reshape(*lead, nb, F)) if return_candidates else f0
+
+
+def stonemask(signal, f0, sample_rate=16000, hop=80, lengths=None):
+    """WORLD's StoneMask refinement of the track f0 [..., F] (Hz; any strides) on signal [T], [B, T] or [B, 1, T] -> fp32 [..., F]: the
+    counterpart of pyworld.stonemask(x, f0, t, fs) with frame i at sample i * hop; tdvc_stonemask (csrc/pitch_dio.hip), one launch,
+    the definition in include/tdvc.h. Frames with f0 not finite, <= 40 Hz or > fs / 12 give 0; a refinement more than 20 % off
+    returns its input. lengths as in `dio` (the window repeats the first and the last valid sample). **Parity with pyworld is
+    unchecked**; the track is fp32 where WORLD's is float64."""
+    x2, x_bs, lead, ln = _world_rows('stonemask', signal, lengths)
+    H.need_device('stonemask', f0)
+    B, T = x2.shape
+    if f0.dim() < 1 or tuple(f0.shape[:-1]) != lead:
+        raise ValueError(f'stonemask: the track must be {list(lead)} + [n_frames], one row per signal row')
+    hop, fs = int(hop), int(sample_rate)
+    if hop < 1 or fs != sample_rate:
+        raise ValueError('stonemask: needs an integer sample rate and hop >= 1')
+    F = f0.shape[-1]
+    f = f0.detach().float()
+    f2 = f if f.dim() == 2 else f.reshape(B, F)
+    out = torch.empty(B, F, dtype=torch.float32, device=x2.device)
+    H.check('stonemask', L.lib().tdvc_stonemask(x2.data_ptr(), x_bs, 1, H.ptr(ln), T, f2.data_ptr(), f2.stride(0) if B > 1 else F,
+                                                 f2.stride(1) if F > 1 else 1, B, F, hop, fs, out.data_ptr(), F, H.stream(x2)))
+    return out.reshape(*lead, F)
+
+
+def world_f0(signal, sample_rate=16000, hop=80, f0_floor=50.0, f0_ceil=500.0, channels_in_octave=2.0, allowed_range=0.1, lengths=None):
+    """stonemask(signal, dio(signal, ...)): the F0 track of the reference's world_analyze, -> fp32 [..., T // hop + 1]. DIO's track
+    passes through one fp32 rounding between the two steps, where WORLD keeps float64. **Parity with pyworld is unchecked.**"""
+    f0 = dio(signal, sample_rate, hop, f0_floor, f0_ceil, channels_in_octave, allowed_range, lengths)
+    return stonemask(signal, f0, sample_rate, hop, lengths)
