@@ -182,17 +182,23 @@ __device__ __forceinline__ void yin_cmdf(const float* dpart, float* red, float* 
   }
 }
 
-// ---- soft search over cl[0 .. n): mn = min c, se = sum_k exp(-100 c[k] + 100 mn), sk = sum_k exp(..) * k, so that
+// Unnormalised softmax weight of a CMDF entry c against the minimum mn: exp(100 (mn - c)). The difference comes first, so the
+// minimum itself weighs exactly 1: a frame whose other weights vanish then has se = 1 and sk = k* exactly, tau = k*, and the
+// backward's (k* - tau) is 0. Written as exp(-100 c + 100 mn) the compiler contracts -100 c + const into an FMA, the argument at the
+// minimum is the rounding error of 100 mn instead of 0, and fl(fl(k* e) / e) can land one ulp off k*: times g_tau * 100 that ulp
+// was the whole gradient of a saturated frame. The forward and the backward both take their weights from here.
+__device__ __forceinline__ float yin_soft_weight(float c, float mn) { return expf((mn - c) * 100.f); }
+
+// ---- soft search over cl[0 .. n): mn = min c, se = sum_k exp(100 (mn - c[k])), sk = sum_k exp(..) * k, so that
 // tau = sk / se where mn is below the threshold. Uses red slots 1..3.
 __device__ __forceinline__ void yin_soft_search(const float* cl, int n, float* red, float& mn, float& se, float& sk) {
   const int tid = threadIdx.x;
   mn = INFINITY;
   for (int k = tid; k < n; k += YIN_THREADS) mn = fminf(mn, cl[k]);
   mn = yin_block_minf(mn, red, 1);
-  const float xmax = -mn * 100.f;
   se = 0.f; sk = 0.f;
   for (int k = tid; k < n; k += YIN_THREADS) {
-    float e = expf(-cl[k] * 100.f - xmax);
+    float e = yin_soft_weight(cl[k], mn);
     se += e;
     sk = fmaf(e, (float)k, sk);
   }

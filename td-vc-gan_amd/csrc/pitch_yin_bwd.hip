@@ -109,7 +109,6 @@ __global__ __launch_bounds__(YIN_THREADS) void yin_soft_bwd_frame_kernel(YinBwdP
 
   // ---- G[m], m = k + 1, k = 4*tid .. 4*tid+3
   {
-    const float xmax = -mn * 100.f;
     const float coef = gy * (-(f0 * f0) / p.sample_rate) * -100.f / se;
     float first[4], suf[4];
 #pragma unroll
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(YIN_THREADS) void yin_soft_bwd_frame_kernel(YinBwdP
       float gc = 0.f, c = 0.f;
       if (kk >= 0 && k < n1) {
         c = cl[kk];
-        gc = coef * expf(-c * 100.f - xmax) * ((float)kk - tau);
+        gc = coef * yin_soft_weight(c, mn) * ((float)kk - tau);
       }
       first[e] = gc * (float)(k + 1) / fmaxf(S[e], YIN_FLOOR);
       suf[e] = (S[e] > YIN_FLOOR) ? gc * c / S[e] : 0.f;       // gc_j j d_j / S_j^2 = gc_j c_j / S_j; no term where the floor is active
