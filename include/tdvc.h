@@ -664,6 +664,61 @@ int tdvc_dio(const float* signal, int64_t s_bs, int64_t s_ts, const int32_t* len
 int tdvc_stonemask(const float* signal, int64_t s_bs, int64_t s_ts, const int32_t* lengths, int32_t T, const float* f0_in, int64_t fi_bs,
                    int64_t fi_fs, int32_t B, int32_t F, int32_t hop, int32_t fs, float* f0_out, int64_t fo_bs, void* stream);
 
+/* Speaker similarity (csrc/eval_speaker.hip): Resemblyzer's VoiceEncoder.embed_utterance with its shipped hparams, the live path
+ * of the reference's test_scripts/common/test_speaker_rec.py, restated here. Resemblyzer, librosa and webrtcvad are not available:
+ * this definition is the contract and the tests pin it; PARITY WITH AN INSTALLED RESEMBLYZER / LIBROSA IS UNCHECKED.
+ *   Constants: sr = 16000, n_fft = 400, hop = 160, n_mels = 40, windows of 160 frames (25600 samples), hidden size 256,
+ *   embedding size 256, 3 layers.
+ *   Windows (compute_partial_slices(n, rate, min_coverage), n = the row's length in samples): n_frames = ceil((n + 1) / 160),
+ *   frame_step = int(round((sr / rate) / 160)) (77 at rate 1.3), steps = max(1, n_frames - 160 + frame_step + 1); window j starts at
+ *   mel frame j frame_step for every j frame_step < steps and covers 160 frames, samples [160 start, 160 (start + 160)); the last
+ *   window is dropped when there is more than one and (n - its first sample) / 25600 < min_coverage (float64 division). The count
+ *   goes 1 -> 2 at n = 31520, 2 -> 3 at 43840, 3 -> 4 at 56160 at the defaults. The row is zero-padded to
+ *   L' = max(n, last window's end). tdvc_voice_window_count is this closed form on the host, the function the kernels call.
+ *   Mel front end (librosa.feature.melspectrogram(y, sr, n_fft=400, hop_length=160, n_mels=40), transposed, of the padded row):
+ *   1 + L' / 160 centred frames, frame f covers padded samples [160 f - 200, 160 f + 200); reflect padding about samples 0 and
+ *   L' - 1 without repeating the edge sample (pad_constant = 0; librosa < 0.10's default) or zeros (pad_constant = 1; librosa
+ *   0.10 and later); samples at and past n count as zero and are never read. Periodic Hann window of 400 points, power |DFT|^2 on
+ *   201 bins, NO LOGARITHM, then the 40 x 201 filterbank librosa.filters.mel(sr, 400, n_mels=40, fmin=0, fmax=sr/2, htk=False,
+ *   norm='slaney'): Slaney mel scale (mel = f / (200/3) below 1000 Hz, 15 + ln(f/1000) / (ln(6.4)/27) above), 42 band edges e
+ *   equally spaced in mel on 0..8000 Hz, triangles max(0, min((f_k - e_i)/(e_{i+1} - e_i), (e_{i+2} - f_k)/(e_{i+2} - e_{i+1}))) at
+ *   f_k = k sr / n_fft, each row scaled by 2 / (e_{i+2} - e_i). `tables` is float64 [400 cos(2 pi i/400) | 400 sin | 400 Hann |
+ *   40 x 201 filterbank], built on the host. Frames at and past 1 + L'/160 of a row are written as zeros. Float64 arithmetic,
+ *   one rounding at the store.
+ *   Volume (normalize_volume(wav, -30 dBFS, increase_only=True)): tdvc_voice_gain writes gain[b] = 10^((-30 - 20 log10 rms)/20)
+ *   where that is > 1 and 1 otherwise, rms over the row's n samples in float64; tdvc_voice_mel multiplies the samples by it
+ *   (gain = NULL: no scaling). Stated deviation: preprocess_wav's silence trimming (webrtcvad) is not reproduced.
+ *   Network: torch.nn.LSTM(I, 256, layers, batch_first=True): gate order i, f, g, o; i, f, o = sigmoid, g = tanh; c' = f c + i g,
+ *   h' = o tanh(c'); zero initial state; both bias vectors added. The top layer's h after the last step, then e = relu(W h + b)
+ *   and e / ||e||_2 without an epsilon (an all-zero e gives NaN, as the reference). Utterance embedding: the mean over the row's
+ *   kept windows of their normalised embeddings, normalised again.
+ * tdvc_voice_windows: counts int32 [B] and slots int32 [B][P_max][2] = (row, start frame) from the device lengths (NULL: T);
+ *   counts are clamped to P_max. tdvc_lstm_fwd: frames fp32 at frames[b f_bs + f f_fs + i], i < I <= 256; slot p is window
+ *   (slots[2p], slots[2p + 1]) and covers T_steps <= 160 frames; with counts, slot p is used when p % P_max < counts[row]; a slot
+ *   whose row or frames lie outside [0, B) x [0, F] is unused as well. h_out fp32 [P][256]: unused slots are ZEROED, frames no
+ *   used window covers are never used (they may hold NaN). weights: 4 pointers per layer, w_ih [1024][I or 256], w_hh [1024][256],
+ *   b_ih, b_hh [1024], fp32 dense. Per layer: two packing launches, the input projection of all frames as one fp32 MFMA GEMM, and
+ *   the recurrence, a workgroup per 16 windows for all steps with W_hh streamed from L2; workgroups never wait for one another.
+ *   tdvc_voice_embed: h [B P_max][256] -> partial [B P_max][256] (zeros for unused slots) and / or utt [B][256].
+ * fp32 throughout the network, exact-fp32 MFMA, accurate expf / tanhf; no atomics, fixed summation orders: bit-identical from call
+ * to call; no allocation, no synchronisation, graph-capturable.
+ * TDVC_EINVAL: negative sizes or strides, frame_step or P_max < 1, NaN min_coverage, null pointers, f_fs < I. TDVC_EUNSUPPORTED:
+ * I > 256, layers outside 1..3, T_steps outside 1..160, more than 2^21 frames (B F) or window steps (P T_steps), T > 2^26,
+ * B > 65535 (mel, gain), reflect padding with T <= 200. TDVC_EWORKSPACE for a null or too small workspace (tdvc_lstm_workspace,
+ * 0 on arguments the call refuses). All before any launch; B == 0 / P == 0 is a no-op. */
+int32_t tdvc_voice_window_count(int64_t n, int32_t frame_step, double min_coverage, int64_t* padded);
+int tdvc_voice_windows(const int32_t* lengths, int32_t T, int32_t B, int32_t frame_step, double min_coverage, int32_t P_max,
+                       int32_t* counts, int32_t* slots, void* stream);
+int tdvc_voice_gain(const float* signal, int64_t s_bs, const int32_t* lengths, int32_t T, int32_t B, double* gain, void* stream);
+int tdvc_voice_mel(const float* signal, int64_t s_bs, const int32_t* lengths, int32_t T, int32_t B, int32_t F, int32_t frame_step,
+                   double min_coverage, int32_t pad_constant, const double* gain, const double* tables, float* mel, void* stream);
+size_t tdvc_lstm_workspace(int32_t B, int32_t F, int32_t I, int32_t P, int32_t T_steps, int32_t layers);
+int tdvc_lstm_fwd(const float* frames, int64_t f_bs, int64_t f_fs, int32_t B, int32_t F, int32_t I, const int32_t* slots,
+                  const int32_t* counts, int32_t P, int32_t P_max, int32_t T_steps, int32_t layers, const float* const* weights,
+                  float* h_out, void* workspace, size_t workspace_bytes, void* stream);
+int tdvc_voice_embed(const float* h, int32_t B, int32_t P_max, const int32_t* counts, const float* W, const float* bias,
+                     float* partial, float* utt, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

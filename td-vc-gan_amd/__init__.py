@@ -8,7 +8,10 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     EQ, RMS-matched) as corrupt_audio / random_eq / sos_filter / peq_sos, with device_batch for the whole batch dict (corrupt.py), and
     load_audio's resampling and segment preparation as resample / load_segments (resample.py), and the objective evaluation of
     test_scripts/common/test_mcd.py as mcd / dtw / fastdtw / mel_cepstrum / sp2mc / sp2mc_matrix / f0_stats, with WORLD's CheapTrick envelope as cheaptrick (evaluate.py)
-    and WORLD's DIO + StoneMask F0 as dio / stonemask / world_f0 (pitch.py; mcd(f0_method='dio')).
+    and WORLD's DIO + StoneMask F0 as dio / stonemask / world_f0 (pitch.py; mcd(f0_method='dio')), and the speaker-similarity
+    evaluation of test_scripts/common/test_speaker_rec.py (Resemblyzer's VoiceEncoder.embed_utterance, per-speaker centroids, cosine
+    similarity and nearest-centroid accuracy) as VoiceEncoder / load_voice_encoder / voice_mel / lstm_fwd / partial_slices /
+    window_count / speaker_similarity (speaker.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -23,7 +26,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -35,6 +38,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.resample'), name)
     if name in ('dtw', 'fastdtw', 'mcd','f0_stats', 'sp2mc', 'sp2mc_matrix', 'mel_cepstrum', 'cheaptrick', 'cheaptrick_mc_matrix'):
         return getattr(importlib.import_module(f'{__name__}.evaluate'), name)
+    if name in ('VoiceEncoder', 'load_voice_encoder', 'voice_mel', 'lstm_fwd', 'partial_slices', 'window_count', 'speaker_similarity'):
+        return getattr(importlib.import_module(f'{__name__}.speaker'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

@@ -190,6 +190,14 @@ SIGNATURES = {
     'tdvc_fastdtw_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'tdvc_fastdtw': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp,
                           _vp, _i64, _vp, C.c_size_t, _vp]),
+    'tdvc_voice_window_count': (C.c_int32, [_i64, C.c_int32, C.c_double, C.POINTER(C.c_int64)]),
+    'tdvc_voice_windows': (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp]),
+    'tdvc_voice_gain': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    'tdvc_voice_mel': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp, _vp]),
+    'tdvc_lstm_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_lstm_fwd': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                           C.POINTER(C.c_void_p), _vp, _vp, C.c_size_t, _vp]),
+    'tdvc_voice_embed': (_i, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),
