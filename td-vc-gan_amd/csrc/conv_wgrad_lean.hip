@@ -7,11 +7,9 @@
 // address in the MFMA loop is base + immediate: one vector add per step. Fragments of step s+1 are fetched
 // before the MFMAs of step s issue.
 #include "launch.h"
+#include "conv_wgrad_frag.h"
 
 namespace tdvc {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 
 constexpr int WG_NTC = 256;
 constexpr int WG_AS = 258;     // 2 (mod 32)
@@ -85,23 +83,8 @@ __global__ __launch_bounds__(256, (M_REP * C_REP * J >= 24 ? 2 : 3)) void conv_w
   const float* a_lane = as + ln * WG_AS + kq + wave * PER_WAVE;
   const float* x_lane = xs + ln * WG_XS + kq + p.i0 + wave * PER_WAVE;
   float av[2][M_REP], bv[2][C_REP][J];
-  auto load_frag = [&](int buf, int nn) {
-#pragma unroll
-    for (int m = 0; m < M_REP; ++m) av[buf][m] = a_lane[nn + m * 16 * WG_AS];
-#pragma unroll
-    for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-      for (int j = 0; j < J; ++j) bv[buf][c][j] = x_lane[nn + c * 16 * WG_XS + j * D];
-  };
-  auto mma = [&](int buf) {
-#pragma unroll
-    for (int m = 0; m < M_REP; ++m)
-#pragma unroll
-      for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-        for (int j = 0; j < J; ++j)
-          acc[m][c][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[buf][m], bv[buf][c][j], acc[m][c][j], 0, 0, 0);
-  };
+  auto load_frag = [&](int buf, int nn) { wg_frag_load<WG_AS, WG_XS, D>(av[buf], bv[buf], a_lane, x_lane, nn); };
+  auto mma = [&](int buf) { wg_frag_mma(av[buf], bv[buf], acc); };
   load_frag(0, 0);
 #pragma unroll 1
   for (int nn = 0; nn < PER_WAVE; nn += 8) {
@@ -143,37 +126,30 @@ __global__ __launch_bounds__(256, (M_REP * C_REP * J >= 24 ? 2 : 3)) void conv_w
     const int ci = c0 + c * 16 + (l & 15);
     if (row < p.R && ci < p.Cin) slab[row * rowlen + (long)ci * p.K + j] = red[idx];
   }
-  if (p.bias_off >= 0 && ct == 0 && (tid & 15) == 0) {
-#pragma unroll
-    for (int i = 0; i < MT / 16; ++i) {
-      const int row = r0 + (tid >> 4) + 16 * i;
-      if (row < p.R) slab[p.bias_off + row] = bias_part[i];
-    }
-  }
+  if (p.bias_off >= 0 && ct == 0) wg_bias_store(bias_part, p, slab, r0, tid);
 }
 
 // ----------------------------------------------------------------------------------------------
-// Register-tile variant for wide layers (R >= 32 and Cin >= 32): the 4 waves form a 2x2 grid over a
-// (32*M_REP) x (32*C_REP) tile of (co, ci) and each keeps its sub-tile (all J taps) in registers while the
-// block walks `tpb` consecutive 64-step time chunks; the operand rows of chunk i+1 are prefetched into
-// registers while the MFMAs of chunk i run (same issue-early / commit-late split as the forward kernel).
-// No cross-wave reduction; one slab per (sample, chunk group).
+// Register-tile variant for the wide layers (R >= 32 and Cin >= 32) that the pipelined kernel (conv_wgrad_pipe.hip)
+// declines: the 4 waves form a 2x2 grid over a (32*M_REP) x (32*C_REP) tile of (co, ci) and each keeps its sub-tile
+// (all J taps) in registers while the block walks `tpb` consecutive 64-step time chunks; the operand rows of chunk
+// i+1 are prefetched into registers while the MFMAs of chunk i run (same issue-early / commit-late split as the
+// forward kernel). No cross-wave reduction; one slab per chunk group.
+// SCAL picks the prefetch (aligned rows with plain prologues never get here, so there is no float4 row prefetch):
+//   1: scalar loads with padding logic for every chunk (unaligned rows, masked dy, reflect); a prologue or span it
+//      does not take (FiLM, span > 128) is staged element-wise without prefetch;
+//   2: contiguous-run float4 loads of short unaligned sequences, one whole sequence per chunk (wt_launch checks the contract).
 constexpr int WT_NTC = 64;
 constexpr int WT_AS = 66;      // 2 (mod 32)
 constexpr int WT_XS = 130;     // 2 (mod 32), >= 64 + 50 + alignment slack
 
-// SCAL = 0: aligned float4 prefetch (long sequences; the chunks at the sequence ends fall back to element-wise
-// staging); SCAL = 1: scalar prefetch with padding logic for every chunk (short / unaligned sequences, masked dy);
-// SCAL: 0 = aligned float4 staging, 1 = scalar staging with padding logic, 2 = contiguous-tile staging of short unaligned rows
 template <int M_REP, int C_REP, int J, int D, int SCAL>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int MT = 32 * M_REP, CT = 32 * C_REP;
-  constexpr int AV = (MT * (WT_NTC / 4) + 255) / 256;       // float4 per thread: dy rows
-  constexpr int XVN = (CT * 32 + 255) / 256;                // float4 per thread: x rows (span <= 128)
+  static_assert(SCAL == 1 || SCAL == 2, "staging modes: 1 = scalar prefetch, 2 = contiguous run");
   constexpr int AS_N = SCAL == 1 ? (MT * WT_NTC + 255) / 256 : 1;   // scalars per thread (unaligned / edge chunks)
   constexpr int XS_N = SCAL == 1 ? (CT * 128 + 255) / 256 : 1;
-  constexpr int AVV = SCAL ? 1 : AV, XVV = SCAL ? 1 : XVN;
   float* as = smem;                     // [MT][WT_AS]
   float* xs = smem + MT * WT_AS;        // [CT][WT_XS]
 
@@ -200,19 +176,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p
   const int q_begin = blockIdx.x * p.tpb, q_end = min(nchunks, q_begin + p.tpb);
   const int avalid = min(MT, p.R - r0), xvalid = min(CT, p.Cin - c0);
   const int akind = p.a.xf.kind, xkind = p.x.xf.kind;
-  // mode per chunk: 2 = aligned float4 prefetch, 1 = scalar prefetch with padding logic, 0 = element-wise fallback
-  const bool vec_kinds = akind <= XF_LRELU && xkind <= XF_LRELU;
-  const bool sc_kinds = (akind <= XF_LRELU || akind == XF_MASK_LRELU) && xkind <= XF_LRELU && p.span <= 128;
-  constexpr bool contig = SCAL == 2;         // mode 3 below (host-checked contract)
-  auto chunk_mode = [&](int q) {
-    const int tile = q % p.ntiles, nc0 = tile * WT_NTC;
-    if (!SCAL) return (p.vec && vec_kinds && nc0 + WT_NTC <= p.N && nc0 + p.lo >= 0 && nc0 + p.lo + p.span <= p.x.T) ? 2 : 0;
+  // mode of the chunk in the prefetch registers: 3 = contiguous-run prefetch (SCAL == 2), 1 = scalar prefetch with padding
+  // logic (SCAL == 1), 0 = nothing prefetched, the chunk is staged element-wise
+  const bool a_plain = akind <= XF_LRELU, x_plain = xkind <= XF_LRELU;
+  const bool sc_kinds = (a_plain || akind == XF_MASK_LRELU) && x_plain && p.span <= 128;
+  constexpr bool contig = SCAL == 2;         // host-checked contract (wt_launch)
+  auto chunk_mode = [&]() {
     if (contig) return 3;
     return sc_kinds ? 1 : 0;
   };
-  RegTile<AVV> ar; RegTile<XVV> xr;
   RegS<AS_N> as_r, as_a; RegS<XS_N> xs_r;
-  // Mode 3 (SCAL == 2): one whole short sequence per chunk (N = T <= 64, e.g. D layer 5: T = 63) whose rows are not 16-byte
+  // SCAL == 2: one whole short sequence per chunk (N = T <= 64, e.g. D layer 5: T = 63) whose rows are not 16-byte
   // aligned. The MT (CT) rows of a tile are still ONE contiguous, 16-byte aligned run of MT*N (CT*T) floats, so they are
   // fetched as float4 of that run (4 / 2 loads per thread instead of 16 / 9 scalar ones with per-element index arithmetic)
   // and scattered to their (row, column) in LDS at the commit. Columns >= N of the dy tile and the halo of the x tile are
@@ -275,26 +249,20 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p
     const int b = q / p.ntiles, nc0 = (q % p.ntiles) * WT_NTC;
     const float* abase = p.a.p + (long)b * p.a.bs + (long)r0 * p.a.T;
     const float* xbase = p.x.p + (long)b * p.x.bs + (long)c0 * p.x.T;
-    if (!SCAL) {
-      tile_issue<AVV>(ar, abase + nc0, p.a.T, avalid, MT, WT_NTC, WT_NTC, 0, tid);
-      tile_issue<XVV>(xr, xbase + nc0 + p.lo, p.x.T, xvalid, CT, p.span, p.span, 0, tid);
-    } else if (SCAL == 1) {
+    if (SCAL == 1) {
       tile_issue_s<AS_N>(as_r, abase, p.N, avalid, MT, WT_NTC, nc0, 0, tid);
       if (akind == XF_MASK_LRELU)
         tile_issue_s<AS_N>(as_a, p.a.xf.aux + (long)b * p.a.xf.aux_bs + (long)r0 * p.a.T, p.N, avalid, MT, WT_NTC, nc0, 0, tid);
       tile_issue_s<XS_N>(xs_r, xbase, p.x.T, xvalid, CT, p.span, nc0 + p.lo, p.reflect, tid);
     }
   };
-  int mode = (q_begin < q_end) ? chunk_mode(q_begin) : 0;
+  int mode = (q_begin < q_end) ? chunk_mode() : 0;
   if (mode) issue(q_begin, mode);
 
   for (int q = q_begin; q < q_end; ++q) {
     const int b = q / p.ntiles, nc0 = (q % p.ntiles) * WT_NTC;
     __syncthreads();
-    if (!SCAL && mode == 2) {
-      tile_commit<AVV>(ar, nullptr, nullptr, p.a.xf, as, WT_AS, avalid, MT, WT_NTC, 0, tid);
-      tile_commit<XVV>(xr, nullptr, nullptr, p.x.xf, xs, WT_XS, xvalid, CT, p.span, 0, tid);
-    } else if (SCAL == 2 && mode == 3) {
+    if (SCAL == 2 && mode == 3) {
       commit_c();
     } else if (SCAL == 1 && mode == 1) {
       tile_commit_s<AS_N>(as_r, &as_a, p.a.xf, as, WT_AS, MT, WT_NTC, tid);
@@ -313,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p
       }
     }
     __syncthreads();
-    mode = (q + 1 < q_end) ? chunk_mode(q + 1) : 0;
+    mode = (q + 1 < q_end) ? chunk_mode() : 0;
     if (mode) issue(q + 1, mode);
 
     if (p.bias_off >= 0 && ct == 0) {
@@ -328,23 +296,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p
     const float* a_lane = as + (wm * 16 * M_REP + ln) * WT_AS + kq;
     const float* x_lane = xs + (wc * 16 * C_REP + ln) * WT_XS + kq + p.i0;
     float av[2][M_REP], bv[2][C_REP][J];
-    auto load_frag = [&](int buf, int nn) {
-#pragma unroll
-      for (int m = 0; m < M_REP; ++m) av[buf][m] = a_lane[nn + m * 16 * WT_AS];
-#pragma unroll
-      for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-        for (int j = 0; j < J; ++j) bv[buf][c][j] = x_lane[nn + c * 16 * WT_XS + j * D];
-    };
-    auto mma = [&](int buf) {
-#pragma unroll
-      for (int m = 0; m < M_REP; ++m)
-#pragma unroll
-        for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-          for (int j = 0; j < J; ++j)
-            acc[m][c][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[buf][m], bv[buf][c][j], acc[m][c][j], 0, 0, 0);
-    };
+    auto load_frag = [&](int buf, int nn) { wg_frag_load<WT_AS, WT_XS, D>(av[buf], bv[buf], a_lane, x_lane, nn); };
+    auto mma = [&](int buf) { wg_frag_mma(av[buf], bv[buf], acc); };
     const int ncols = min(WT_NTC, ((p.N - nc0) + 7) & ~7);      // skip the all-zero tail of a short last tile
     load_frag(0, 0);
 #pragma unroll 1
@@ -373,13 +326,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_tile_kernel(const WgLeanP p
         }
       }
     }
-  if (p.bias_off >= 0 && ct == 0 && (tid & 15) == 0) {
-#pragma unroll
-    for (int i = 0; i < MT / 16; ++i) {
-      const int row = r0 + (tid >> 4) + 16 * i;
-      if (row < p.R) slab[p.bias_off + row] = bias_part[i];
-    }
-  }
+  if (p.bias_off >= 0 && ct == 0) wg_bias_store(bias_part, p, slab, r0, tid);
 }
 
 template <int M_REP, int C_REP, int J, int D, int SCAL>
@@ -409,10 +356,7 @@ static hipError_t wg_launch(const WgLeanP& p, int B, hipStream_t st) {
 
 template <int M_REP, int C_REP, int J, int D>
 static hipError_t wt_launch(const WgLeanP& p, int B, hipStream_t st) {
-  // aligned long sequences with plain prologues -> float4 prefetch; everything else -> scalar prefetch
-  const bool vec = p.vec && p.a.xf.kind <= XF_LRELU && p.x.xf.kind <= XF_LRELU && p.N >= 2 * WT_NTC;
-  if (vec) return wt_launch2<M_REP, C_REP, J, D, 0>(p, B, st);
-  // contiguous-tile staging (kernel, mode 3): one whole short sequence per chunk, full tiles, rows back to back, zero padding, tiles
+  // contiguous-run staging (SCAL = 2): one whole short sequence per chunk, full tiles, rows back to back, zero padding, tiles
   // that start on 16-byte boundaries (D layer 5: 1024 -> 1024, T = 63)
   constexpr int MT = 32 * M_REP, CT = 32 * C_REP;
   auto al16 = [](const void* ptr) { return (((uintptr_t)ptr) & 15) == 0; };
@@ -429,19 +373,24 @@ static hipError_t wg_launch_jd(WgLeanP& p, int B, hipStream_t st) {
   wgrad_lean_plan(p.R, p.Cin, p.N, p.K, B, &p.ntiles, &p.tpb, &p.ngroups);
   p.B = B;
   if (p.R <= 16 || p.Cin <= 16) return wg_launch<1, 1, J, D>(p, B, st);
-  if (J == 15) return hipErrorNotSupported;      // 15-tap layers on the path are narrow (D layer 0: 1 -> 16)
-  {   // aligned rows with plain / FiLM prologues: the pipelined kernel (conv_wgrad_pipe.hip)
-    const hipError_t e = launch_conv_wgrad_pipe(p, J, D, st);
-    if (e != hipErrorNotSupported) return e;
+  // every tile choice that J alone decides is `if constexpr`: only the instances a call can reach are built
+  if constexpr (J == 15) {
+    return hipErrorNotSupported;      // 15-tap layers on the path are narrow (D layer 0: 1 -> 16)
+  } else {
+    {   // aligned rows with plain / FiLM prologues: the pipelined kernel (conv_wgrad_pipe.hip)
+      const hipError_t e = launch_conv_wgrad_pipe(p, J, D, st);
+      if (e != hipErrorNotSupported) return e;
+    }
+    // wide layers: 64-step chunks, register tile per wave
+    p.span = ((WT_NTC + (J - 1) * D - p.pad - p.lo) + 3) / 4 * 4;
+    if constexpr (J <= 3) {
+      if (!wgrad_prefers_ct32(p.Cin))
+        return p.R <= 32 ? wt_launch<1, 2, J, D>(p, B, st)      // 32 x 64 block tile, 16 x 32 per wave
+                         : wt_launch<2, 2, J, D>(p, B, st);     // 64 x 64 block tile, 32 x 32 per wave
+    }
+    return p.R <= 32 ? wt_launch<1, 1, J, D>(p, B, st)          // 32 x 32 block tile
+                     : wt_launch<2, 1, J, D>(p, B, st);         // 64 x 32 block tile, 32 x 16 per wave
   }
-  // wide layers: 64-step chunks, register tile per wave
-  p.span = ((WT_NTC + (J - 1) * D - p.pad - p.lo) + 3) / 4 * 4;
-  if (p.R <= 32) {
-    if (J <= 3 && !wgrad_prefers_ct32(p.Cin)) return wt_launch<1, 2, J, D>(p, B, st);    // 32 x 64 block tile, 16 x 32 per wave
-    return wt_launch<1, 1, J, D>(p, B, st);                 // 32 x 32 block tile
-  }
-  if (J <= 3 && !wgrad_prefers_ct32(p.Cin)) return wt_launch<2, 2, J, D>(p, B, st);      // 64 x 64 block tile, 32 x 32 per wave
-  return wt_launch<2, 1, J, D>(p, B, st);                   // 64 x 32 block tile, 32 x 16 per wave
 }
 
 // Grid plan shared by the workspace query and the launch: chunk length, chunks per block, chunk groups per sample.

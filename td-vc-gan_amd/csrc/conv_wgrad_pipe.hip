@@ -15,13 +15,12 @@
 //   * bias-gradient row sums are accumulated from the registers on their way into LDS.
 // x' prologues: none / LeakyReLU, or FiLM (h*(1+gamma)+beta -> LeakyReLU, three streams) for the 1x1 posconv.
 #include "conv_common.h"
-#include "conv_wgrad_lean.h"
+#include "conv_wgrad_frag.h"
 
 PROF_DEFINE(tdvc_debug_wgrad_prof)
 
 namespace tdvc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WP_NTC = 64;
@@ -195,23 +194,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const WgLeanP p
     const float* a_lane = st_cur + (wm * 16 * M_REP + ln) * WP_AS + kq;
     const float* x_lane = st_cur + MT * WP_AS + (wc * 16 * C_REP + ln) * XSW + kq + p.i0;
     float av[2][M_REP], bv[2][C_REP][J];
-    auto load_frag = [&](int buf, int nn) {
-#pragma unroll
-      for (int m = 0; m < M_REP; ++m) av[buf][m] = a_lane[nn + m * 16 * WP_AS];
-#pragma unroll
-      for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-        for (int j = 0; j < J; ++j) bv[buf][c][j] = x_lane[nn + c * 16 * XSW + j * D];
-    };
-    auto mma = [&](int buf) {
-#pragma unroll
-      for (int m = 0; m < M_REP; ++m)
-#pragma unroll
-        for (int c = 0; c < C_REP; ++c)
-#pragma unroll
-          for (int j = 0; j < J; ++j)
-            acc[m][c][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[buf][m], bv[buf][c][j], acc[m][c][j], 0, 0, 0);
-    };
+    auto load_frag = [&](int buf, int nn) { wg_frag_load<WP_AS, XSW, D>(av[buf], bv[buf], a_lane, x_lane, nn); };
+    auto mma = [&](int buf) { wg_frag_mma(av[buf], bv[buf], acc); };
     load_frag(0, 0);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -299,13 +283,18 @@ static hipError_t wp_launch(WgLeanP& p, hipStream_t st) {
 template <int J, int D>
 static hipError_t wp_launch_jd(WgLeanP& p, hipStream_t st) {
   p.span = ((WP_NTC + (J - 1) * D - p.pad - p.lo) + 3) / 4 * 4;
-  const bool ct64 = J <= 3 && !wgrad_prefers_ct32(p.Cin);   // 64 input channels per block tile unless that pads too much (136)
-  if (p.R <= 32 || J >= 11) {                             // (11 taps: the 64-row tile would spill its accumulators)
-    if (ct64) return wp_launch<1, 2, J, D>(p, st);       // 32 x 64 block tile, 16 x 32 per wave
-    return wp_launch<1, 1, J, D>(p, st);                  // 32 x 32 block tile
+  // every tile choice that J alone decides is `if constexpr`: only the instances a call can reach are built
+  if constexpr (J <= 3) {
+    if (!wgrad_prefers_ct32(p.Cin))                         // 64 input channels per block tile unless that pads too much (136)
+      return p.R <= 32 ? wp_launch<1, 2, J, D>(p, st)       // 32 x 64 block tile, 16 x 32 per wave
+                       : wp_launch<2, 2, J, D>(p, st);      // 64 x 64 block tile, 32 x 32 per wave
   }
-  if (ct64) return wp_launch<2, 2, J, D>(p, st);         // 64 x 64 block tile, 32 x 32 per wave
-  return wp_launch<2, 1, J, D>(p, st);                    // 64 x 32 block tile, 32 x 16 per wave
+  if constexpr (J >= 11) {
+    return wp_launch<1, 1, J, D>(p, st);                    // (11 taps: the 64-row tile would spill its accumulators)
+  } else {
+    return p.R <= 32 ? wp_launch<1, 1, J, D>(p, st)         // 32 x 32 block tile
+                     : wp_launch<2, 1, J, D>(p, st);        // 64 x 32 block tile, 32 x 16 per wave
+  }
 }
 
 // Contract: p.vec (16-byte aligned rows, N % 4 == 0), dy' prologue none / LeakyReLU, x' prologue none / LeakyReLU /

@@ -1,5 +1,5 @@
 """Edge geometry of the stride-1 'same' WEIGHT-GRAD family against float64: conv_wgrad_lean_kernel<1,1,J,D> (narrow layers),
-conv_wgrad_tile_kernel<M,C,J,D,SCAL> in its three staging modes, conv_wgrad_pipe_kernel<M,C,J,D,XFILM> and the split-bf16
+conv_wgrad_tile_kernel<M,C,J,D,SCAL> in its two staging modes, conv_wgrad_pipe_kernel<M,C,J,D,XFILM> and the split-bf16
 conv_wgrad_x6_kernel, each with the slab fold (bias partials behind the weights) that ends the call.
 
 Same rules as test_generic_conv_edges_gpu.py, whose Edge this file drives: fp32-valued inputs, float64 autograd on the same numbers,
