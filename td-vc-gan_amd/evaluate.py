@@ -368,7 +368,11 @@ def _voiced_cepstra(who, sig, length, f0, sample_rate, hop, drop_c0, envelope, m
     if length is None:
         valid = torch.ones(B, F, dtype=torch.bool, device=sig.device)
     else:
-        nfr = torch.div(length.to(sig.device) + (hop - 1), hop, rounding_mode='floor')      # frames centred inside the row
+        ln = length.to(sig.device)
+        if cheap or f0_method == 'dio':                                           # WORLD's frame grid: f * hop <= length, 1 + length // hop frames
+            nfr = 1 + torch.div(ln, hop, rounding_mode='floor')
+        else:                                                                     # frames centred inside the row: f * hop < length
+            nfr = torch.div(ln + (hop - 1), hop, rounding_mode='floor')
         valid = torch.arange(F, device=sig.device)[None, :] < nfr[:, None]
     f0 = torch.where(valid, f0, torch.zeros_like(f0))
     if drop_c0:
@@ -392,7 +396,11 @@ def mcd(test, ref, test_len=None, ref_len=None, sample_rate=16000, f0_test=None,
     align='fastdtw' the call is then the reference's pipeline, step for step, as the same algorithms.
     Frame alignment: STFT frame f and YIN frame f are both centred on sample f * hop (the STFT reflects n_fft/2 samples, YIN
     zero-pads half a frame), so frame f of one is frame f of the other; the STFT has one frame more when T is a multiple of
-    hop, and the common frames are kept. With a length, the frames centred inside the row, f * hop < length, count.
+    hop, and the common frames are kept. With a length, the frames centred inside the row, f * hop < length, count. Where a WORLD
+    component supplies the frame grid (f0_method='dio' or envelope='cheaptrick') the frame set is WORLD's, f * hop <= length: the
+    1 + length // hop frames of `world_f0` and of `mel_cepstrum`'s n_frames, so a length that is a multiple of hop keeps the frame
+    centred on sample `length` (its window repeats the last valid sample), and a row gives the same numbers with length = T as
+    without a length.
     The voiced frames of each side are compacted on the device and aligned with metric 'l2': align='exact' (the default) by `dtw`,
     the exact programme (at most 4096 frames, 20.5 s); align='fastdtw' by `fastdtw` with `radius`, the reference's alignment as the
     same algorithm (at most 16384 frames; parity with the installed fastdtw package is unchecked, and its pyramid is fp32 here).
