@@ -167,3 +167,16 @@ def assert_update_matches_fixture(models, gold_npz, before, lr, what=''):
     assert frac <= 0.01, f'{what}: {frac:.4f} of the sampled elements moved differently by more than lr/2'
     assert rel <= 2e-2, f'{what}: rel-L2 of the sampled update (well-conditioned elements) = {rel:.3e}'
     return frac, rel
+
+
+def update_stats(before, after_got, after_ref, lr):
+    """Agreement of two AdamW updates of one tensor. Early Adam steps are ~ -lr * sign(g) per element, so an element whose
+    gradient is below its own fp32 noise may legitimately land 2*lr apart: report the fraction of such elements and the
+    rel-L2 over the rest."""
+    d_got = (after_got.double().cpu() - before.double()).reshape(-1)
+    d_ref = (after_ref.double() - before.double()).reshape(-1)
+    diff = (d_got - d_ref).abs()
+    flipped = diff > 0.5 * lr
+    ok = ~flipped
+    rel_rest = float((d_got[ok] - d_ref[ok]).norm() / (d_ref[ok].norm() + 1e-30)) if ok.any() else 0.0
+    return float(flipped.double().mean()), rel_rest, float(d_ref.norm())

@@ -7,7 +7,7 @@ import importlib
 
 import pytest
 
-from test_film_cond_bwd_edges_gpu import CASES, COND0, FUSED, NV
+from film_cond_cases import CASES, COND0, FUSED, NV
 
 CHUNK = {FUSED: 60, COND0: 64}
 

@@ -2,7 +2,7 @@
 one launch, 16 channels) through ctypes, against float64. test_fused_film_block_forward_is_bit_identical compares the kernel with the
 two-launch path through ops.FilmBlockFn (contiguous operands, K in {3, 7, 11}); this file checks the contract itself.
 
-Rules (those of test_generic_conv_edges_gpu.py):
+Rules (those of test_generic_conv_edges_gpu.py; the rows, their data and the float64 reference are in film_block_ref.py):
 
   * Inputs hold fp32 values; the references are float64 on the same numbers.
   * h = float64 reflect-padded dilated conv of lrelu(x), plus b1; bars with n = 16 K, A = conv(|lrelu(x)|, |w1|), slack 8.
@@ -29,68 +29,15 @@ import ctypes as C
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from common import rel_l2, traced
-from test_generic_conv_edges_gpu import SENT, SLOPE, U, _mods, assert_bars, elem_check
+from edge_support import EINVAL, EUNSUPPORTED, SENT, SLOPE, U, Worst, assert_bars, elem_check, lib, mods, poison_lds, stream
+from film_block_ref import ROWS, block_data, conv_h64, out64
 
 pytestmark = pytest.mark.gpu
-EINVAL, EUNSUPPORTED = -1, -4
 GUARD = 64
 NAN = float('nan')
-
-# name: (K, d, T, options); B = 3, C = 16
-ROWS = {r[0]: r[1:] for r in [
-    ('k3_d1_T512_film_acc_views', 3, 1, 512, dict(film=True, acc=True, views=True)),      # the minimum T, everything strided
-    ('k11_d5_T516_nofilm', 11, 5, 516, dict(film=False, acc=True)),      # the third tile has 4 columns, its whole left halo lies in tile 1
-    ('k7_d3_T764_film', 7, 3, 764, dict(film=True, acc=False, views=True)),      # a 252-column last tile
-    ('k15_d2_T520_nobias_scale0', 15, 2, 520, dict(film=True, acc=True, b1=False, b2=False, scale=0.0)),      # wnp == FB_WVP; scale 0 means 1
-    ('k13_d5_T640_span80', 13, 5, 640, dict(film=True, acc=False)),      # span / 4 == 80 == FB_XSP
-    ('k3_d31_T512_span80', 3, 31, 512, dict(film=False, acc=False, views=True)),      # the same limit by dilation
-    # even K with pad 3; acc and out are views while x, h and gb are contiguous: five batch strides of two kinds
-    ('k4_d2_T512_even', 4, 2, 512, dict(film=True, acc=True, views=('acc', 'y'))),
-    ('k1_d7_T512_nohalo', 1, 7, 512, dict(film=True, acc=False, views=True)),      # no halo
-]}
-WORST = {}      # kernel -> tensor -> (err / bound, row)
-
-
-def lrelu(t):
-    return F.leaky_relu(t, SLOPE)
-
-
-def conv_h64(x, w1, b1, K, d):
-    """float64 h: reflect-padded dilated conv of lrelu(x) plus b1, and the same on absolute values (without the bias)."""
-    pad = (K - 1) * d // 2
-    assert 2 * pad == (K - 1) * d
-    padr = (lambda t: F.pad(t, (pad, pad), mode='reflect')) if pad else (lambda t: t)
-    h = F.conv1d(padr(lrelu(x.double())), w1.double(), b1.double() if b1 is not None else None, dilation=d)
-    return h, F.conv1d(padr(lrelu(x.double()).abs()), w1.double().abs(), None, dilation=d)
-
-
-def out64(h, x, gb, w2, b2, acc, scale):
-    """float64 out from a given h (fp32 values of the GPU, or float64), and A of its bound; also (h2, H) for the kink assertion."""
-    h = h.double()
-    if gb is not None:
-        ga, be = gb.double()[:, :16], gb.double()[:, 16:]
-        h2, H = h * (1 + ga) + be, h.abs() * (1 + ga.abs()) + be.abs()
-    else:
-        h2, H = h, h.abs()
-    w = w2.double().view(16, 16, 1)
-    z = F.conv1d(lrelu(h2), w, b2.double() if b2 is not None else None) + x.double()
-    A = F.conv1d(H, w.abs(), b2.double().abs() if b2 is not None else None) + x.double().abs()
-    out, A = scale * z, scale * A
-    if acc is not None:
-        out, A = out + acc.double(), A + acc.double().abs()
-    return out, A, h2, H
-
-
-def block_data(name, K, d, T, B=3, C_=16, film=True, acc=True, b1=True, b2=True, scale=1.0 / 3, **_):
-    """The fp32-valued inputs of a row (CPU), seeded by its name."""
-    gen = torch.Generator().manual_seed(sum(map(ord, name)))
-    rnd = lambda *sh: torch.randn(*sh, generator=gen).float()
-    return dict(x=rnd(B, C_, T), w1=rnd(C_, C_, K) / (C_ * K) ** 0.5, b1=rnd(C_) * 0.1 if b1 else None, w2=rnd(C_, C_) / C_ ** 0.5,
-                b2=rnd(C_) * 0.1 if b2 else None, gb=rnd(B, 2 * C_, T) * 0.5 if film else None, acc=rnd(B, C_, T) if acc else None,
-                scale=scale, eff_scale=scale if scale != 0.0 else 1.0)
+WORST = Worst()      # kernel -> tensor -> (err / bound, row)
 
 
 def gbuf(B, Cc, T, dev, views, fill, src=None, lead=0, bs=None):
@@ -132,7 +79,7 @@ class Block:
         self.names = set()
 
     def args(self, **over):
-        L = _mods()[1]
+        L = mods()[1]
         pb = lambda t: (t.data_ptr(), t.stride(0)) if t is not None else (None, 0)
         v = dict(B=self.B, C=self.C, T=self.T, K=self.K, d=self.d, w1=self.w1.data_ptr())
         v.update(over)
@@ -141,10 +88,9 @@ class Block:
                                self.data['scale'], SLOPE, *pb(self.y))
 
     def call(self, **over):
-        lib = _mods()[1].lib()
         a = self.args(**over)
         with traced() as tr:
-            rc = lib.tdvc_film_block_fwd(C.byref(a), torch.cuda.current_stream(self.dev).cuda_stream)
+            rc = lib().tdvc_film_block_fwd(C.byref(a), stream(self.dev))
         self.names = tr.names
         return rc
 
@@ -167,7 +113,7 @@ class Block:
 
     def two_launch(self):
         """h and out of the two tdvc_conv_fwd calls FilmBlockFn's fallback makes, on the same input buffers."""
-        ops, L, arena = _mods()
+        ops, L, arena = mods()
         cs = ops.ConvSpec(16, 16, self.K, 1, (self.K - 1) * self.d // 2, self.d, 1, True)
         cs.slot = arena.ConvSlot(self.w1.data_ptr(), self.b1.data_ptr() if self.b1 is not None else 0, 0, 0, False, None, 0)
         ps = ops.ConvSpec(16, 16, 1)
@@ -183,21 +129,18 @@ def test_film_block_row(name, dev):
     """Every accepted row: rc 0, the instance by trace and nothing else, both bars on h and out, nothing written outside the two
     operands, bit-identical to the two-launch fallback; once more on NaN-poisoned LDS."""
     K, d, T, opts = ROWS[name]
-    L = _mods()[1]
     for poison in (False, True):
         blk = Block(name, K, d, T, dev, **opts)
         if poison:
-            L.check(L.lib().tdvc_debug_poison_lds(0xFFFFFFFF, torch.cuda.current_stream(dev).cuda_stream))
+            poison_lds(dev)
         rc = blk.call()
-        assert rc == 0, (rc, L.lib().tdvc_last_error())
+        assert rc == 0, (rc, lib().tdvc_last_error())
         kern = 'film_block_fwd_kernel<true>' if opts.get('film') else 'film_block_fwd_kernel<false>'
         assert blk.names == {kern}, sorted(blk.names)
         assert untouched(blk.h_flat, blk.h) and untouched(blk.y_flat, blk.y), 'the kernel wrote outside h / out'
         res = blk.bars()
         assert_bars(res, name + (' (poisoned LDS)' if poison else ''))
-        for k, v in res.items():
-            if v['ratio'] >= WORST.setdefault(kern, {}).get(k, (-1.0, ''))[0]:
-                WORST[kern][k] = (v['ratio'], name)
+        WORST.note(kern, res, name)
         with traced() as tr:
             h2, out2 = blk.two_launch()
         assert not any(n.startswith('film_block_fwd_kernel') for n in tr.names), sorted(tr.names)
@@ -227,26 +170,24 @@ def test_film_block_refusal(name, dev):
     """Outside the contract: the return code, nothing launched, every output and guard still SENT. The buffers are sized for the refused
     geometry (32 channels where C = 32 is asked for), so a launch that slipped through would stay inside them."""
     K, d, T, bopts, over, want = REFUSALS[name]
-    lib = _mods()[1].lib()
     blk = Block(name, K, d, T, dev, **bopts)
     if blk.C != 16:      # w2 for the refused channel count
         blk.w2 = torch.randn(blk.C, blk.C, device=dev)
     over = dict(over)
     tile = over.pop('force_tile', None)
     if tile is not None:
-        lib.tdvc_debug_force_tile(tile)
+        lib().tdvc_debug_force_tile(tile)
     try:
         rc = blk.call(**over)
     finally:
-        lib.tdvc_debug_force_tile(-1)
+        lib().tdvc_debug_force_tile(-1)
     torch.cuda.synchronize()
-    assert rc == want, (name, rc, lib.tdvc_last_error())
+    assert rc == want, (name, rc, lib().tdvc_last_error())
     assert not blk.names, sorted(blk.names)
     assert blk.outputs_untouched(), 'a refused call wrote to h / out or their guards'
 
 
 def test_zz_worst_error_film_block():
     """Prints the worst err / bound per kernel and tensor over the rows that ran in this session (asserted row by row)."""
-    for kern, per in sorted(WORST.items()):
-        print(f'[edge] worst {kern}: ' + '  '.join(f'{k} {r:.3f} ({n})' for k, (r, n) in sorted(per.items())))
-    assert all(r <= 1.0 for per in WORST.values() for r, _ in per.values())
+    WORST.report()
+    assert all(r <= 1.0 for r in WORST.ratios())

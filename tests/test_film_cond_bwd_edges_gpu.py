@@ -3,7 +3,7 @@ backward behind cond_var.2's output gradient) and film_cond0_bwd_kernel (film_co
 dk3_fold_kernel and the slab fold that close the call. Both entry points are driven through the C ABI (tdvc_film_cond_bwd,
 tdvc_film_cond0_bwd): ops.FilmCondFn's gates (sign bits only at T >= 512, contiguous operands, n_cond = 136) hide most of the contract.
 
-Same rules as test_generic_conv_edges_gpu.py, whose helpers this file uses: fp32-valued inputs, a float64 CPU reference on the same
+Same rules as test_generic_conv_edges_gpu.py, with the helpers of edge_support.py: fp32-valued inputs, a float64 CPU reference on the same
 numbers, dw0 ACCUMULATED onto random values, dexc and dk3 starting as SENT, the workspace exactly the queried bytes inside a
 SENT-guarded buffer, operands that may be channel slices of wider buffers, and both bars on every tensor:
     rel-L2 < 2e-5   and   |got - ref| <= (n + 8) * 2^-23 * A + 2^-22 * |ref|
@@ -11,7 +11,7 @@ SENT-guarded buffer, operands that may be channel slices of wider buffers, and b
 Every case asserts by trace the exact kernel, dk3_fold_kernel iff a workspace was given, slab_reduce_multi_kernel iff dw0 was given,
 and nothing else.
 
-test_cond_plan_cpu.py imports CASES and checks the plan figures quoted in the table (chunks per block, blocks, straddling) on the CPU.
+The table is CASES of film_cond_cases.py; test_cond_plan_cpu.py checks the plan figures quoted in it (chunks per block, blocks, straddling) on the CPU.
 """
 import ctypes as C
 
@@ -20,79 +20,19 @@ import torch
 import torch.nn.functional as F
 
 from common import rel_l2, traced
-from test_generic_conv_edges_gpu import SENT, _buf, _mods, _spare_intact, assert_bars, elem_check
+from edge_support import (EINVAL, EUNSUPPORTED, EWORKSPACE, SENT, Worst, _buf, _spare_intact, assert_bars, elem_check, mods, pack_sign_bits,
+                          poison_lds)
+from film_cond_cases import BITS_ROWS, CASES, COND0, FUSED, NV, REFUSAL_BASE, ROWS
 
 pytestmark = pytest.mark.gpu
 
-NV = 8                                   # excitation channels: the last 8 input channels of cond_var.0
-EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -2, -4
-FUSED, COND0 = 'fused', 'cond0'
 FOLD, SLAB = 'dk3_fold_kernel', 'slab_reduce_multi_kernel'
-
-# name, (nc, C2, T, B), options. Every row runs on the fused kernel (chunks of 60 steps + a 2-column halo either side) and on
-# cond0 (chunks of 64) unless `only` says otherwise. Options: mask = 'bits' (fused: sign words, cv0 = NULL) | 'fp32';
-# views: dgb, exc, dexc, cv0 / dcv are channel slices [:, :C] of [B, C + 4, T] buffers; bits_views: the sign words are a slice of
-# [B, nc + 2, T / 32]; dexc / dw / ws = False: that pointer is NULL; slope: LeakyReLU slope of the mask (0.2).
-CASES = {c[0]: c for c in [
-    # minimum of every dimension; the dk3 deltas at t = 0 and t = T - 1 in one k-step; one 12-row channel tile, eight empty ones
-    ('min_T4', (12, 32, 4, 3), dict()),
-    # exactly one channel tile; exactly one fused chunk (column 61 = T - 1); cond0: 60 of 64 columns
-    ('one_tile_nc16', (16, 32, 60, 2), dict()),
-    # nw = 1: words 1, 2 of every 3-word window are out of range
-    ('bits_T32', (136, 32, 32, 5), dict(mask='bits')),
-    # fused chunk 1 (n0 = 60) wants words 1 .. 3 of 3; cond0: the second chunk is 32 wide
-    ('bits_T96_past_last_word', (136, 64, 96, 3), dict(mask='bits')),
-    # fused: the second chunk has 4 columns and holds the T - 1 delta; cond0: exactly one chunk
-    ('seam_T64', (100, 32, 64, 3), dict()),
-    # cond0: the second chunk has 4 columns
-    ('seam_T68', (72, 32, 68, 2), dict()),
-    # fused chunk 1 ends on T - 1: the generic indicator path of stage (b)
-    ('T120_not_interior', (136, 32, 120, 2), dict()),
-    # fused chunk 1 is interior (constant-indicator fast path), chunk 2 has 4 columns
-    ('T124_interior', (136, 32, 124, 2), dict()),
-    # full 144 rows, no zero tile; an interior chunk on the bits path; the last fused chunk is 8 wide; cond0: two exact chunks
-    ('bits_T128', (144, 32, 128, 2), dict(mask='bits')),
-    # six reduction steps of the software-pipelined d_cv0 product
-    ('ncc6', (136, 96, 64, 2), dict()),
-    # ten steps; 140 = 8 3/4 channel tiles
-    ('ncc10_nc140', (140, 160, 64, 2), dict(mask='bits')),
-    # every batch stride wider than contiguous; the spare channels of dexc stay SENT; fused: cv0 once more 4 bytes off alignment
-    ('views', (136, 64, 132, 3), dict(views=True)),
-    # cv0_sign_bits_bs
-    ('bits_views', (136, 32, 64, 3), dict(mask='bits', bits_views=True)),
-    # stage (a) and its barrier skipped; dk3 and dW0 unchanged against the reference
-    ('no_dexc', (136, 32, 124, 2), dict(dexc=False)),
-    # slots at offset 0 of the workspace; no slab fold, the dw0 buffer bit-identical
-    ('no_dw_ws', (136, 32, 124, 3), dict(dw=False)),
-    # atomics into the zeroed dk3
-    ('no_dw_no_ws', (136, 32, 124, 3), dict(dw=False, ws=False)),
-    # a hard-coded 0.2
-    ('slope_001', (136, 32, 64, 2), dict(slope=0.01, only=FUSED)),
-    # both plans: 3 chunks per sample, 600 chunks, tpb = 2, 300 blocks: every other block crosses a sample; dk3 from two slots per sample
-    ('walk_tpb2_straddle_bits', (136, 32, 160, 200), dict(mask='bits')),
-    # 1 chunk per sample, tpb = 3, 344 blocks, the last with one chunk: a block covers three samples and flushes dk3 every chunk;
-    # slot 4k + 3 is never written and must never be read
-    ('walk_tpb3_three_samples', (136, 32, 32, 1030), dict(mask='bits')),
-    # fused: 2 chunks per sample, 1040 chunks, tpb = 3, 347 blocks, the last with two; cond0: tpb = 2, 260 blocks of two whole samples
-    ('walk_tpb3_fp32', (136, 64, 64, 520), dict()),
-]}
-# not a row of the table: the valid call the refusal tests start from (views: every operand sits inside a wider buffer; T % 32 == 0)
-REFUSAL_BASE = ('refusal_base', (136, 64, 64, 3), dict(views=True))
-ROWS = [(n, w) for n, c in CASES.items() for w in (FUSED, COND0) if c[2].get('only', w) == w]
-BITS_ROWS = [n for n, c in CASES.items() if c[2].get('mask') == 'bits']
-WORST = {}                               # kernel -> tensor -> (err / bound, case)
+WORST = Worst()                          # kernel -> tensor -> (err / bound, case)
 _DATA = {}                               # (case, which) -> inputs and float64 references, computed once and never modified
 
 
 def _row(name):
     return REFUSAL_BASE if name == REFUSAL_BASE[0] else CASES[name]
-
-
-def pack_sign_bits(cv0):
-    """[B][nc][T] -> int32 words [B][nc][T / 32], bit t % 32 of word t / 32 set where cv0 > 0 (test_sign_bit_masks' expression)."""
-    B, nc, T = cv0.shape
-    w = ((cv0 > 0).reshape(B, nc, T // 32, 32).long() << torch.arange(32)).sum(-1)
-    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
 
 
 def _convT(x, w):
@@ -194,7 +134,7 @@ class CondEdge:
 
     def args(self, ws_ptr, ws_bytes, **over):
         """The argument struct of the case; `over` replaces fields (the refusal tests)."""
-        L = _mods()[1]
+        L = mods()[1]
         f = dict(B=self.B, T=self.T, n_cond=self.nc, n_var=NV, exc=self.exc.data_ptr(), exc_bs=self.exc.stride(0), w0=self.w0.data_ptr(),
                  dexc=self.dexc.data_ptr() if self.with_dexc else None, dexc_bs=self.dexc.stride(0), dk3=self.dk3.data_ptr(),
                  dw0=self.dw0.data_ptr() if self.with_dw else None, workspace=ws_ptr, workspace_bytes=ws_bytes)
@@ -211,7 +151,7 @@ class CondEdge:
     def call(self, ws_short=0, with_ws=None, **over):
         """One call -> rc. The workspace is exactly the queried size (less `ws_short` bytes) inside a larger SENT-filled buffer;
         self.guard_ok says whether the bytes around the region are still SENT afterwards."""
-        L = _mods()[1]
+        L = mods()[1]
         lib = L.lib()
         q = lib.tdvc_film_cond_bwd_workspace if self.which == FUSED else lib.tdvc_film_cond0_bwd_workspace
         self.query = q(self.B, self.T, self.nc, NV)
@@ -261,7 +201,7 @@ class CondEdge:
 
     def run(self, tag=''):
         rc = self.call()
-        assert rc == 0, (rc, _mods()[1].lib().tdvc_last_error())
+        assert rc == 0, (rc, mods()[1].lib().tdvc_last_error())
         assert self.guard_ok, f'wrote outside the {self.query}-byte workspace'
         want = {self.kernel()} | ({FOLD} if self.with_ws else set()) | ({SLAB} if self.with_dw else set())
         assert self.names == want, (self.name, self.which, sorted(self.names), sorted(want))
@@ -269,9 +209,7 @@ class CondEdge:
         assert_bars(res, f'{self.kernel()}: {self.name}{tag}')
         if self.with_dw:      # the embedding window really is part of the checked tensor
             assert int((self.d['A']['dw0'] == 0).sum()) == self.nc * (self.nc - NV) * 3
-        for k, v in res.items():
-            if v['ratio'] >= WORST.setdefault(self.kernel(), {}).get(k, (-1.0, ''))[0]:
-                WORST[self.kernel()][k] = (v['ratio'], self.name)
+        WORST.note(self.kernel(), res, self.name)
         return res
 
 
@@ -294,8 +232,7 @@ def test_cond_bwd_edge(name, which, dev):
 def test_cond_bwd_edge_poisoned_lds(name, which, dev):
     """Every row once more on NaN-poisoned LDS: the zero rows >= n_cond of the staged W2^T chunk, of the W0 window and of the sign-word
     table, the pad columns of the staging tiles and the sign words past the last one must come from the kernel, not from what LDS held."""
-    L = _mods()[1]
-    L.check(L.lib().tdvc_debug_poison_lds(0xFFFFFFFF, torch.cuda.current_stream(dev).cuda_stream))
+    poison_lds(dev)
     e = CondEdge(name, which, dev)
     e.run(' (poisoned LDS)')
     assert all(bool(torch.isfinite(t).all()) for t in (e.dk3, e.dw0) + ((e.dexc,) if e.with_dexc else ()))
@@ -358,7 +295,7 @@ def _refusal(what, which, dev):
     over = change(e) if callable(change) else change if isinstance(change, dict) else {}
     rc = e.call(with_ws=change != 'no_ws', ws_short=4 if change == 'short_ws' else 0, **over)
     torch.cuda.synchronize()
-    assert rc == code, (what, which, rc, _mods()[1].lib().tdvc_last_error())
+    assert rc == code, (what, which, rc, mods()[1].lib().tdvc_last_error())
     assert not e.names, sorted(e.names)
     assert e.guard_ok and bool((e.dexc_whole == SENT).all()) and bool((e.dk3 == SENT).all()), 'a refused call wrote an output'
     assert torch.equal(e.dw0.cpu(), e.d['dw0_start']), 'a refused call wrote dw0'
@@ -378,5 +315,4 @@ def test_cond0_refusals(what, dev):
 
 def test_zz_worst_error_by_kernel():
     """Prints the worst err / bound per kernel and tensor over the cases that ran in this session (asserted case by case)."""
-    for kernel, per in sorted(WORST.items()):
-        print(f'[edge] worst {kernel}: ' + '  '.join(f'{k} {r:.3f} ({n})' for k, (r, n) in sorted(per.items())))
+    WORST.report()

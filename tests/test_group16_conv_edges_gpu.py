@@ -1,10 +1,10 @@
 """Edge geometry of the MFMA kernels for grouped stride-4 convs with 4 input and 16 output channels per group
 (group16_fwd_kernel / group16_dgrad_kernel, conv_small_group.hip: discriminator layers 1-3) against float64, through the Edge
-class of test_generic_conv_edges_gpu.py: both bars on every tensor (rel-L2 < 2e-5 and the element-wise summation bound), the
+class of conv_edge.py (rules: test_generic_conv_edges_gpu.py): both bars on every tensor (rel-L2 < 2e-5 and the element-wise summation bound), the
 kernel names of every call, NaN-poisoned LDS before every case.
 
 Every case runs the forward, the input-grad twice (dy_xf NONE and MASK_LRELU, both with the PLAIN epilogue the route takes) and the
-weight-grad, which stays on its present route. The input-grad goes straight through conv_dgrad_raw, because Edge.dgrad() ties the
+weight-grad, which stays on its present route. The input-grad goes straight through conv_dgrad_raw (plain_dgrad of conv_edge.py), because Edge.dgrad() ties the
 dy transform to the case's `post` option: its float64 reference is the transposed conv of dy' = dy * out_scale (* lrelu'(aux)),
 with aux = the stored forward output, whatever activation the case has.
 
@@ -16,10 +16,10 @@ switch) assert the generic conv_gemm_kernel by name, and right results.
 """
 import pytest
 import torch
-import torch.nn.functional as F
 
-from common import rel_l2, traced
-from test_generic_conv_edges_gpu import SENT, SLOPE, Edge, _mods, _spare_intact, assert_bars, elem_check
+from common import traced
+from conv_edge import Edge, plain_dgrad
+from edge_support import assert_bars, mods, poison_lds
 
 pytestmark = pytest.mark.gpu
 
@@ -58,35 +58,11 @@ CASES = {
 OFF_ROUTE = ('conv_gemm_kernel', 'weight_repack_kernel', 'conv_scalar_kernel', 'small_group_')
 
 
-def poison(dev):
-    L = _mods()[1]
-    L.check(L.lib().tdvc_debug_poison_lds(0xFFFFFFFF, torch.cuda.current_stream(dev).cuda_stream))
-
-
 def make_case(name, dev):
     g, opts, out_scale = CASES[name]
     e = Edge(g, dev, **opts)
     e.out_scale = out_scale      # Edge ties out_scale to `add`; the forward call, its reference and dy_xf all read the attribute
     return e
-
-
-def plain_dgrad(e, masked):
-    """tdvc_conv_dgrad with the PLAIN epilogue and dy_xf NONE / MASK_LRELU (aux = the stored forward output) -> (bars, kernel names)."""
-    ops, L, _ = _mods()
-    (_, cin, cout, k, s, p, d, g, _, _, _, T) = e.geom
-    xf = ops._xf(L.XF_MASK_LRELU, scale=e.out_scale, aux=e.yv) if masked else ops._xf(scale=e.out_scale)
-    e.dxv.fill_(SENT)
-    with traced() as tr:
-        ops.conv_dgrad_raw(e.spec, e.dyv, xf, T, L.DG_PLAIN, out=e.dxv)
-    assert _spare_intact(e.dx_whole, cin), 'input-grad wrote into the spare channels behind dx'
-    dyp = e.cot.double() * e.out_scale
-    if masked:
-        dyp = dyp * torch.where(e.yv.detach().cpu() > 0, 1.0, SLOPE).double()
-    out_pad = T - ((e.tout - 1) * s - 2 * p + k)
-    ref = F.conv_transpose1d(dyp, e.w.double(), None, stride=s, padding=p, output_padding=out_pad, groups=g)
-    A = F.conv_transpose1d(dyp.abs(), e.w.double().abs(), None, stride=s, padding=p, output_padding=out_pad, groups=g)
-    ratio, inexact = elem_check(e.dxv, ref, A, cout // g * k)
-    return {'dx_masked' if masked else 'dx': dict(rel=rel_l2(e.dxv, ref), ratio=ratio, inexact=inexact)}, tr.names
 
 
 def assert_route(names, kernel, what):
@@ -97,7 +73,7 @@ def assert_route(names, kernel, what):
 @pytest.mark.parametrize('name', list(CASES))
 def test_group16_edge(name, dev):
     """Forward and input-grad on the new kernels (by name; no generic kernel, no weight repack), weight-grad on its present route."""
-    poison(dev)
+    poison_lds(dev)
     e = make_case(name, dev)
     (_, cin, cout, k, s, p, d, g, _, _, _, T) = e.geom
     if name == 'walk':      # the shape really makes a wave walk two tiles, and the last walk of a row is partial, in both kernels
@@ -128,8 +104,8 @@ DECLINE = {
 
 @pytest.mark.parametrize('name', list(DECLINE))
 def test_group16_declines_to_generic(name, dev):
-    L = _mods()[1]
-    poison(dev)
+    L = mods()[1]
+    poison_lds(dev)
     g, opts = DECLINE[name]
     e = Edge(g, dev, **opts)
     if name == 'knob_off':
@@ -148,8 +124,8 @@ def test_group16_declines_to_generic(name, dev):
 @pytest.mark.parametrize('name', ['one_over', 'unaligned', 'k9', 'views', 'walk'])
 def test_group16_bits_of_generic_route(name, dev):
     """y and dx (dy_xf NONE and MASK_LRELU) are bit-identical with the route on and off (tdvc_debug_knob(2, 1): conv_gemm_kernel)."""
-    ops, L, _ = _mods()
-    poison(dev)
+    ops, L, _ = mods()
+    poison_lds(dev)
     e = make_case(name, dev)
     T = e.geom[-1]
     post = (L.POST_NONE, L.POST_LRELU)[e.post]

@@ -23,34 +23,17 @@ import importlib
 import pytest
 import torch
 
-import test_conv_ops_gpu as OPS
+import conv_ops_cases as OPS
 from common import rel_l2, traced
+from edge_support import TOL, forced_tile, mods
+from lean_cases import EPI_FILM, EPI_FWD, EPI_MASK, EPI_PLAIN, LEAN_CFG, LXF_ACT, LXF_FILM, LXF_MASK_LRELU, lean_name
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-5
-
-LEAN_CFG = {0: (1, 4, 1, 4), 1: (2, 4, 1, 4), 2: (4, 4, 1, 4), 3: (1, 1, 1, 4), 4: (1, 4, 4, 1), 5: (3, 4, 1, 4), 6: (1, 2, 2, 2), 7: (9, 1, 1, 4)}
-LXF_ACT, LXF_FILM, LXF_MASK_LRELU = 0, 1, 2
-EPI_FWD, EPI_MASK, EPI_FILM, EPI_PLAIN = 0, 1, 2, 3
-
-
-def _L():
-    return importlib.import_module('td-vc-gan_amd')._lib
-
-
-def lean_name(cfg, xfk, epi):
-    m, n, wm, wn = LEAN_CFG[cfg]
-    return f'conv_lean_kernel<{m},{n},{wm},{wn},{xfk},{epi}>'
 
 
 def _run_forced(cfg, fn):
-    L = _L()
-    L.lib().tdvc_debug_force_tile(cfg)
-    try:
-        with traced() as tr:
-            errs = fn()
-    finally:
-        L.lib().tdvc_debug_force_tile(-1)
+    with traced() as tr:
+        errs = forced_tile(cfg, fn)
     return errs, tr.names
 
 
@@ -184,7 +167,7 @@ def test_launch_shape_fused_conditioning(cfg, fused_fwd, fused_bwd, dev):
     fused launch (tdvc_film_cond_fwd, prologue kind LXF_COND); backward as the step's ONE launch behind cond_var.2's output
     gradient (tdvc_film_cond_bwd: the 136-channel gradient stays on chip; mask from the forward's sign bits, or from the fp32
     intermediate where T % 32 != 0) and as the two-launch path it replaces (cond_var.2 input-grad + tdvc_film_cond0_bwd)."""
-    ops = importlib.import_module('td-vc-gan_amd').ops
+    ops = mods()[0]
     old = ops.FUSED_COND_FWD, ops.FUSED_COND_BWD
     ops.FUSED_COND_FWD, ops.FUSED_COND_BWD = fused_fwd, fused_bwd
     try:
@@ -220,7 +203,7 @@ def test_folded_short_sequences(case, B, dev):
     assert max(errs.values()) < TOL, (errs, sorted(tr.names))
     folded = [n for n in tr.names if n.startswith('conv_lean_kernel') and n.endswith(',true>')]
     assert len(folded) >= 2, sorted(tr.names)          # forward and input-grad both run folded tiles
-    lib = importlib.import_module('td-vc-gan_amd')._lib.lib()
+    lib = mods()[1].lib()
     lib.tdvc_debug_knob(4, 1)                          # the same case unfolded: same results up to the accumulation order
     try:
         errs1 = OPS.conv_case_errors(case, dev, 0, B=B)
@@ -247,7 +230,7 @@ def test_split_bf16_x6_weight_grad(case, B, dev):
         errs = OPS.conv_case_errors(case, dev, 0, B=B)
     assert max(errs.values()) < TOL, (errs, sorted(tr.names))
     assert 'conv_wgrad_x6_kernel' in tr.names, sorted(tr.names)
-    lib = importlib.import_module('td-vc-gan_amd')._lib.lib()
+    lib = mods()[1].lib()
     lib.tdvc_debug_knob(5, 1)                          # exact-fp32 MFMA path on the same case
     try:
         with traced() as tr1:
@@ -297,8 +280,7 @@ def test_split_bf16_x6_forward_weight_cache(dev):
     """The cached bf16 weight pieces follow the arena's weights: they key on arena.version, which every materialize() bumps. A stale
     cache would reproduce the old output exactly; here the layer's weight is scaled by 1.5 in place between two forwards."""
     from common import build_models
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, L = P.ops, P._lib
+    ops, L, _ = mods()
     G, _ = build_models(dev)
     ar = G.ensure_arena(dev)
     name, mod = next((n, m) for n, m in G.named_modules() if n.endswith('cond_var.2') and m.spec.cout >= ops.X6_FWD_MIN_COUT and m.spec.cout % 32 == 0)
@@ -334,8 +316,7 @@ COND_FWD_X6 = [(136, 32, 1024, 3, True), (136, 64, 500, 2, False), (72, 96, 128,
 @pytest.mark.parametrize('nc,C2,T,B,with_bits', COND_FWD_X6, ids=[f'nc{a}_C{b}_T{c}' for a, b, c, _, _ in COND_FWD_X6])
 def test_fused_cond_forward_x6(nc, C2, T, B, with_bits, dev):
     import ctypes as C
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena, L = P.ops, P.arena, P._lib
+    ops, L, arena = mods()
     lib = L.lib()
     torch.manual_seed(nc + C2 + T)
     nv = 8
@@ -385,8 +366,7 @@ def test_fused_cond_forward_x6(nc, C2, T, B, with_bits, dev):
 def test_fused_cond_forward_x6_matches_two_launches(dev):
     """ops.film_cond with the fused forward vs the two-launch forward: same gb and same gradients (dexc, dk3, weight gradients) within fp32
     rounding -- the backward consumes the fused kernel's cv0 / sign bits."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena, L = P.ops, P.arena, P._lib
+    ops, L, arena = mods()
     torch.manual_seed(77)
     B, nc, nv, C2, T = 3, 136, 8, 64, 1024
     w0 = (torch.randn(nc, nc, 3) / (nc * 3) ** 0.5).to(dev)
@@ -432,8 +412,7 @@ SIGN_CFG = [-1, 0, 1, 2, 4, 5, 6, 3]      # 3 = one sub-tile per wave: the launc
 
 @pytest.mark.parametrize('cfg', SIGN_CFG, ids=[f'tile{c}' for c in SIGN_CFG])
 def test_sign_bit_masks(cfg, dev):
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena, L = P.ops, P.arena, P._lib
+    ops, L, arena = mods()
     torch.manual_seed(100 + cfg)
     B, cin, cmid, cout, T = 3, 8, 40, 24, 544
     w0 = (torch.randn(cmid, cin, 3) / (cin * 3) ** 0.5).to(dev)
@@ -477,8 +456,7 @@ def test_sign_bit_masks(cfg, dev):
 
 def test_sign_bits_refused_outside_contract(dev):
     """Shapes that cannot carry the words (T % 32 != 0) are refused, not silently computed without the bits."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena, L = P.ops, P.arena, P._lib
+    ops, L, arena = mods()
     w = torch.randn(16, 8, 3, device=dev)
     s = ops.ConvSpec(8, 16, 3, 1, 1, 1, 1, False)
     s.slot = arena.ConvSlot(w.data_ptr(), 0, 0, 0, False, None, 0)
@@ -492,8 +470,7 @@ def test_sign_bits_refused_outside_contract(dev):
 # tdvc_conv_fwd / tdvc_conv_dgrad try small-group, lean, generic in that order; these pin the edges between lean and generic.
 def test_lean_shaped_conv_off_the_vector_contract_runs_generic(dev):
     """pw_c64 (64 -> 64, k = 1, T = 333) is lean-shaped, but T % 4 != 0 and T > 80: the generic MFMA kernel takes it."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena, L = P.ops, P.arena, P._lib
+    ops, L, arena = mods()
     case = next(c for c in OPS.CASES if c[0] == 'pw_c64')
     with traced() as tr:
         errs = OPS.conv_case_errors(case, dev, 0, B=2)
@@ -511,8 +488,7 @@ def test_lean_shaped_conv_off_the_vector_contract_runs_generic(dev):
 def _mask_dgrad_40_24(dev, T):
     """Input-grad of a 40 -> 24, k = 3, pad 1 conv at B = 2 with the LeakyReLU-mask epilogue: (spec, dy, x_in, sign words of x_in,
     the weight tensors the spec points into)."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, arena = P.ops, P.arena
+    ops, _, arena = mods()
     torch.manual_seed(T)
     w = (torch.randn(24, 40, 3) / 120 ** 0.5).to(dev)
     wt = w.permute(1, 0, 2).contiguous()
@@ -525,8 +501,7 @@ def _mask_dgrad_40_24(dev, T):
 
 def test_sign_bit_dgrad_off_contract_retries_with_fp32_mask(dev):
     """T = 520 is vector-aligned but T % 32 != 0: the lean launch with the sign words declines and the same launch runs on x_in."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, L = P.ops, P._lib
+    ops, L, _ = mods()
     s, dy, y, bits, _w = _mask_dgrad_40_24(dev, 520)
     with traced() as tr:
         dx_bits = ops.conv_dgrad_raw(s, dy, ops._xf(), 520, L.DG_MASK_LRELU, x_in=y, x_bits=bits)
@@ -538,8 +513,7 @@ def test_sign_bit_dgrad_off_contract_retries_with_fp32_mask(dev):
 
 def test_sign_bit_dgrad_without_x_in_refused_off_contract(dev):
     """The same call without the fp32 mask source has nothing to retry with: refused, nothing launched."""
-    P = importlib.import_module('td-vc-gan_amd')
-    ops, L = P.ops, P._lib
+    ops, L, _ = mods()
     s, dy, _, bits, _w = _mask_dgrad_40_24(dev, 520)
     with traced() as tr:
         with pytest.raises(L.TdvcError):

@@ -1,5 +1,5 @@
-"""CPU-side checks of the two edge suites test_lean_conv_edges_gpu.py and test_film_block_fwd_edges_gpu.py: what their GPU cases rely
-on but a GPU run would not tell apart from a kernel defect.
+"""CPU-side checks of the two edge suites test_lean_conv_edges_gpu.py and test_film_block_fwd_edges_gpu.py (their tables and mirrors:
+lean_cases.py, film_block_ref.py): what their GPU cases rely on but a GPU run would not tell apart from a kernel defect.
 
   * every seeded case passes its kink assertion (a case that does not would fail on the GPU for a reason of the data);
   * the film-block float64 reference equals a naive loop nest at (K, d, T) = (3, 2, 12), C = 16;
@@ -10,10 +10,11 @@ on but a GPU run would not tell apart from a kernel defect.
 import pytest
 import torch
 
-import test_film_block_fwd_edges_gpu as FB
-import test_lean_conv_edges_gpu as LE
-from test_generic_conv_edges_gpu import SLOPE, U, Edge
-from test_kernel_instances_gpu import LEAN_CFG
+import film_block_ref as FB
+import lean_cases as LE
+from conv_edge import Edge
+from edge_support import SLOPE, U
+from lean_cases import LEAN_CFG
 
 CPU = torch.device('cpu')
 SEEDED = {**{n: c[:2] for n, c in LE.CASES.items()}, LE.WINDOW[0][0]: LE.WINDOW, **{n: c[:2] for n, c in LE.FILM_K3.items()},

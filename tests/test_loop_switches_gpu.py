@@ -9,8 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import build_models, filled_sd, pkg, to_dev
-from test_step_launch_shape_gpu import update_stats
+from common import build_models, filled_sd, pkg, to_dev, update_stats
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3

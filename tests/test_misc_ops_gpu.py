@@ -16,14 +16,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import rel_l2
+from common import rel_l2
+from edge_support import EINVAL, SENT, stream
 
 pytestmark = pytest.mark.gpu
 EW = 1e-6          # element-wise: |got - ref| <= EW * (magnitude of the combined terms)
 TOL = 2e-5         # reductions: rel-L2 per tensor
 LOSS = 1e-5        # loss scalars: rel
-SENT = -7777.25    # sentinel: every output buffer starts filled with it
-EINVAL = -1
 
 
 def _pkg():
@@ -32,10 +31,6 @@ def _pkg():
 
 def _lib():
     return _pkg()._lib
-
-
-def _st(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def f32(x):
@@ -90,7 +85,7 @@ def _adamw_run(dev, n, wd, gscale, device_step, steps, max_norm=None):
     max_norm: each step first computes the clip coefficient on the device (tdvc_grad_clip_coef) and updates with
     tdvc_adamw_clipped; the reference scales its gradient by the coefficient the kernel computed."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     wd = f32(wd)
     gen = torch.Generator().manual_seed(1000 + n % 997 + (7 if device_step else 0) + int(wd > 0) * 3 + int(gscale != 1.0) * 5)
     p0 = torch.randn(n, generator=gen)
@@ -173,7 +168,7 @@ def test_grad_clip_coef(n, gscale, norm, active, dev):
     """out[0] = min(1, max_norm / (gscale ||g|| + 1e-6)), out[1] = gscale ||g||. n > 1024 * 256 caps the partial-sum count at
     1024; a norm of 2e-3 makes the 1e-6 visible at the loss bar."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     gen = torch.Generator().manual_seed(n + int(norm))
     g = torch.randn(n, generator=gen)
     g = (g * (norm / float(g.norm()))).float()
@@ -241,7 +236,7 @@ def test_weight_norm_fwd_and_transposed_copy(dev):
     """tdvc_weight_norm_fwd / _fwd_t against float64 g v / ||v||; the transposed copy checked element by element against the
     arena's layout [cin][rows][K] at w_off, nothing else of either arena written."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     ts_, params, tb, nrows, n_w = _wn_setup(dev)
     assert nrows % 4 != 0
     W = torch.full((n_w,), SENT, device=dev)
@@ -277,7 +272,7 @@ def test_weight_norm_bwd(accumulate, dev):
     """tdvc_weight_norm_bwd against float64 autograd of g v / ||v|| with a random upstream dW: dv and dg written (0) or added
     (1) at the parameter offsets, every other parameter-gradient element untouched."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     ts_, params, tb, nrows, n_w = _wn_setup(dev)
     gen = torch.Generator().manual_seed(12)
     dW = torch.randn(n_w, generator=gen)
@@ -316,7 +311,7 @@ def test_mse_const(n, up, dev):
     """loss += weight mean((x - target)^2); dx = 2 weight / n (x - target) upstream (upstream NULL = 1). x is a view one float
     into its buffer."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     gen = torch.Generator().manual_seed(n)
     x = torch.randn(n, generator=gen)
     target, weight = f32(0.75), f32(1.7)
@@ -349,7 +344,7 @@ def _l1_inputs(n, seed):
 def test_l1_single(n, accumulate, dev):
     """tdvc_l1_fwd / tdvc_l1_bwd: loss += weight mean|a - b|; da (+)= sign(a - b) weight / n upstream, sign(0) = 0."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     a, b = _l1_inputs(n, n + 1)
     weight, up = f32(0.35), 1.9
     ab, ad = _padded(a, dev)
@@ -377,7 +372,7 @@ def test_l1_single(n, accumulate, dev):
 def test_cross_entropy(K, B, dev):
     """tdvc_cross_entropy_fwd / _bwd against float64 F.cross_entropy (mean over the batch) at logits of +-80, labels 0 and K-1."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     gen = torch.Generator().manual_seed(K * 10 + B)
     z = torch.randn(B, K, generator=gen) * 3
     if K >= 3:
@@ -442,7 +437,7 @@ def test_contrastive_vs_float64(shape, dev):
     if shape[2] == 294:
         assert _lds_floats(C_, T, N) * 4 <= 150 * 1024 < _lds_floats(C_, T + 1, N) * 4
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     LS = _pkg().losses
     gen = torch.Generator().manual_seed(B * 1000 + C_ * 10 + T + N)
     X = torch.randn(B, C_, T, generator=gen)
@@ -475,7 +470,7 @@ def test_contrastive_refuses_lds_overflow(dev):
     idx = torch.zeros(B, T, N, dtype=torch.int32, device=dev)
     out = torch.zeros(1, device=dev)
     rc = L.lib().tdvc_contrastive_fwd_bwd(X.data_ptr(), X.data_ptr(), idx.data_ptr(), idx.data_ptr(), B, C_, T, N, 1.0, out.data_ptr(),
-                                          X.data_ptr(), X.data_ptr(), _st(dev))
+                                          X.data_ptr(), X.data_ptr(), stream(dev))
     assert rc == L.EUNSUPPORTED
 
 
@@ -492,7 +487,7 @@ def _reflect_cases():
 def test_reflect_pad(T, pad, dev):
     """tdvc_reflect_pad_fwd (bit-exact) / _bwd (the mirrored taps folded back) against F.pad(mode='reflect') and its autograd."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, Tp = 3, T + 2 * pad
     gen = torch.Generator().manual_seed(T * 7 + pad)
     x = torch.randn(B, T, generator=gen)
@@ -517,15 +512,15 @@ def test_reflect_pad_refuses_pad_ge_T(dev):
     L = _lib()
     x = torch.zeros(2, 64, device=dev)
     y = torch.zeros(2, 64 * 3, device=dev)
-    assert L.lib().tdvc_reflect_pad_fwd(x.data_ptr(), y.data_ptr(), 2, 64, 64, _st(dev)) == EINVAL
-    assert L.lib().tdvc_reflect_pad_bwd(y.data_ptr(), x.data_ptr(), 2, 64, 64, _st(dev)) == EINVAL
+    assert L.lib().tdvc_reflect_pad_fwd(x.data_ptr(), y.data_ptr(), 2, 64, 64, stream(dev)) == EINVAL
+    assert L.lib().tdvc_reflect_pad_bwd(y.data_ptr(), x.data_ptr(), 2, 64, 64, stream(dev)) == EINVAL
 
 
 @pytest.mark.parametrize('B,Fq,N', [(1, 3, 5), (2, 1028, 257)], ids=['tiny', 'nfft2048_capped_grid'])
 def test_power(B, Fq, N, dev):
     """power [B][F][N] = re^2 + im^2 of spec [B][2F][N] (re rows, then im rows); dspec = 2 dpower spec."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     gen = torch.Generator().manual_seed(Fq)
     spec = torch.randn(B, 2 * Fq, N, generator=gen)
     dpw = torch.randn(B, Fq, N, generator=gen)
@@ -554,7 +549,7 @@ def _log_l1_ref(a, b, weight, up):
 
 def _log_l1_run(a, b, weight, up, dev):
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     n = a.numel()
     ab, ad = _padded(a, dev)
     bd = b.to(dev)
@@ -653,7 +648,7 @@ def test_l2norm(C_, dev):
     """tdvc_l2norm_fwd / _bwd against float64 F.normalize(dim=1, eps=1e-12) and its autograd; T = 300 (not a multiple of 256)
     with an all-zero column."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, T = 2, 300
     eps = f32(1e-12)
     gen = torch.Generator().manual_seed(C_)
@@ -688,7 +683,7 @@ def test_gather_ch(dev):
     """tdvc_gather_ch_fwd: y[b][t] = x[b][label_b][t]; _bwd: dx[b][c][t] = dy[b][t] on the label's channel, 0 on the others
     (every element written). Labels 0 and C - 1."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, C_, T = 3, 5, 300
     gen = torch.Generator().manual_seed(3)
     x = torch.randn(B, C_, T, generator=gen)
@@ -710,7 +705,7 @@ def test_gather_ch(dev):
 def test_concat_cond(accumulate, dev):
     """tdvc_concat_cond: c = cat(emb repeated over T, exc) (bit-exact); _bwd: demb (+)= sum_t dc[:, :Ce], dexc = dc[:, Ce:]."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, Ce, Cx, T = 3, 128, 8, 300
     gen = torch.Generator().manual_seed(4 + accumulate)
     emb = torch.randn(B, Ce, generator=gen)
@@ -734,7 +729,7 @@ def test_concat_cond(accumulate, dev):
 def test_edge_sum3(T, dev):
     """out[b][c] = (d[..., 0], sum d[..., 1:T-1], d[..., T-1])."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, C_ = 2, 5
     d = torch.randn(B, C_, T, generator=torch.Generator().manual_seed(T))
     dd = d.to(dev)
@@ -751,14 +746,14 @@ def test_edge_sum3_refuses_T_below_3(dev):
     L = _lib()
     d = torch.zeros(2, 5, 3, device=dev)
     out = torch.zeros(2, 5, 3, device=dev)
-    assert L.lib().tdvc_edge_sum3(d.data_ptr(), out.data_ptr(), 2, 5, 2, _st(dev)) == EINVAL
+    assert L.lib().tdvc_edge_sum3(d.data_ptr(), out.data_ptr(), 2, 5, 2, stream(dev)) == EINVAL
 
 
 @pytest.mark.parametrize('T', [257, 20000])
 def test_roll_batches(T, dev):
     """y[b] = torch.roll(x[b], shift[b], -1) for shifts 0, +-1, T-1, +-T, +-(3T+5). T = 20000 > 64 * 256: the capped grid strides."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     shifts = [0, 1, -1, T - 1, T, -T, 3 * T + 5, -(3 * T + 5)]
     B, C_ = len(shifts), 3
     x = torch.randn(B, C_, T, generator=torch.Generator().manual_seed(T))
@@ -783,7 +778,7 @@ def test_gate(B, H, T, with_g, dev):
     """tdvc_gate_fwd / _bwd (acts = tanh(a) sigmoid(s) of the WaveNet stack) with every batch stride wider than contiguous;
     the gaps between samples stay untouched."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     HT = H * T
     gen = torch.Generator().manual_seed(H + T + with_g)
     xin = torch.randn(B, 2 * H, T, generator=gen) * 1.5
@@ -818,7 +813,7 @@ def test_gate(B, H, T, with_g, dev):
 def test_axpby_and_fill(n, with_b, dev):
     """tdvc_axpby: y = alpha a + beta b (b NULL: alpha a); tdvc_fill: y = value; unaligned views, nothing outside written."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     gen = torch.Generator().manual_seed(n + with_b)
     a, b = torch.randn(n, generator=gen), torch.randn(n, generator=gen)
     alpha, beta = f32(-0.7), f32(1.3)
@@ -870,7 +865,7 @@ def test_film_k3_vs_float64(n_const, nblk, multi, dev):
     summed over them) against float64 conv1d autograd. B = 7 (not a multiple of the forward's 4 samples per block); dw0 / db0
     are added into (+=), and dw0's columns of the non-constant input channels stay untouched."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B = 7
     nc, emb_bs, emb_full, emb, w0, b0, dk3, dw_pre, db_pre = _k3_case(n_const, nblk, B)
     ed = emb_full.to(dev)
@@ -908,7 +903,7 @@ def test_film_k3_vs_float64(n_const, nblk, multi, dev):
 def test_film_k3_refuses_n_const_above_256(dev):
     """The forward keeps a weight row of <= 256 constant channels in registers: 257 -> TDVC_EINVAL before any launch."""
     L = _lib()
-    lib, st = L.lib(), _st(dev)
+    lib, st = L.lib(), stream(dev)
     B, n_const, nc = 2, 257, 265
     emb = torch.zeros(B, n_const, device=dev)
     w0 = torch.zeros(nc, nc, 3, device=dev)

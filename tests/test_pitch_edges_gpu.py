@@ -44,6 +44,7 @@ import torch
 import yin_edges_ref as ER
 import yin_grad_ref as GR
 from common import pkg
+from edge_support import poison_lds
 
 pytestmark = pytest.mark.gpu
 SR, THR = ER.SR, ER.THR
@@ -206,16 +207,12 @@ def test_yin_edges_backward_c_entry_writes_all_and_nothing_else(dev, name):
 def test_yin_edges_poisoned_lds(dev, name):
     """The LDS of every CU pre-filled with NaN bit patterns before the forward and before the backward: finite, and the clean run's
     bits. A read of LDS that the kernel has not written, landing anywhere but in a term a select discards, shows up as NaN."""
-    L = pkg()._lib
-
-    def poison():
-        L.check(L.lib().tdvc_debug_poison_lds(0xFFFFFFFF, torch.cuda.current_stream(dev).cuda_stream))
     for soft in (False, True):
-        poison()
+        poison_lds(dev)
         f0, c = run_forward(name, soft)
         assert bool(torch.isfinite(f0).all()) and bool(torch.isfinite(c).all())
         assert torch.equal(f0, device_forward(name, soft)[0]) and torch.equal(c, device_forward(name, soft)[1])
-    poison()
+    poison_lds(dev)
     dx, f0 = run_backward(name)
     assert bool(torch.isfinite(dx).all())
     assert torch.equal(dx, device_backward(name)[0]) and torch.equal(f0, device_backward(name)[1])

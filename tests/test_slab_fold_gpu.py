@@ -6,7 +6,7 @@ Every case runs the production kernel (float4 groups, the loads of up to 8 slabs
 loop it replaced on equal inputs and requires
   * equal bits of the two results, gaps and guards included: the production kernel keeps the reference's order of additions
     per element (slab s0 .. s1-1 inside a y-block, then the y-blocks' partials in order);
-  * the result within the fp32 bound of a sum of nslab + 1 terms against float64 (elem_check of test_generic_conv_edges_gpu:
+  * the result within the fp32 bound of a sum of nslab + 1 terms against float64 (elem_check of edge_support:
     (terms + 8) * 2^-23 * sum|terms| + 2^-22 |ref|) and rel-L2 < 2e-5;
   * the sentinel in the columns between mapped rows and in the guards around dw / dbias.
 
@@ -19,10 +19,9 @@ import pytest
 import torch
 
 from common import rel_l2, traced
-from test_generic_conv_edges_gpu import elem_check
+from edge_support import SENT, elem_check
 
 pytestmark = pytest.mark.gpu
-SENT = -7777.25
 GUARD = 8
 KERNEL = 'slab_reduce_multi_kernel'
 

@@ -1,12 +1,12 @@
 """Edge geometry of the vector-ALU kernels for grouped strided convs with 4 input and 4 output channels per group
 (small_group_fwd_kernel<S>, small_group_dgrad_kernel<S>, small_group_wgrad_kernel, conv_small_group.hip: discriminator layer 4)
-against float64, through the Edge class of test_generic_conv_edges_gpu.py: both bars on every tensor (rel-L2 < 2e-5 and the
+against float64, through the Edge class of conv_edge.py (rules: test_generic_conv_edges_gpu.py): both bars on every tensor (rel-L2 < 2e-5 and the
 element-wise summation bound with exact zeros where A == 0), NaN-poisoned LDS before every case, outputs that start as SENT, the
 weight-grad workspace exactly as large as the query says with a guard around it, and the kernel of every call asserted by name.
 
-The case table, with the edge each row sits on, is CASES of test_small_group_plan_cpu.py (host-side checks of the same table run
-there without a GPU). Every case runs the forward, the input-grad twice (dy_xf NONE and MASK_LRELU with the PLAIN epilogue: the
-only forms the route takes; plain_dgrad of the group16 suite) and the weight-grad. What the rows reach that nothing else does:
+The case table, with the edge each row sits on, is CASES of small_group_cases.py (test_small_group_plan_cpu.py runs host-side checks of
+the same table without a GPU). Every case runs the forward, the input-grad twice (dy_xf NONE and MASK_LRELU with the PLAIN epilogue: the
+only forms the route takes; plain_dgrad of conv_edge.py) and the weight-grad. What the rows reach that nothing else does:
 
   * Tout = 64 / 65 (tile boundary of the forward, 4 * Tout == 256 limit of the weight-grad and the first shape past it);
   * pad % 4 != 0 (scalar dx stores, a lane that straddles t = 0), odd Tin, channel-slice views with unaligned planes;
@@ -18,7 +18,7 @@ only forms the route takes; plain_dgrad of the group16 suite) and the weight-gra
   * the off switch (tdvc_debug_knob(2, 1)): all three calls on the generic kernels.
 
 tanh. The term device tanhf adds to the y bar is measured as the lean suite measures it: on ANOTHER kernel, the scalar generic
-route on the same case (tanh_excess of test_lean_conv_edges_gpu.py). TANH_EXCESS_MEASURED is that figure in units of 2^-24; the bar
+route on the same case (tanh_excess of conv_edge.py). TANH_EXCESS_MEASURED is that figure in units of 2^-24; the bar
 allows twice that (test_tanh_allowance_measured_on_scalar_route repeats the measurement and prints it).
 
 RESULTS (first run on an MI355X; every figure is err / bound, the bar is 1.0)
@@ -49,10 +49,9 @@ RESULTS (first run on an MI355X; every figure is err / bound, the bar is 1.0)
 """
 import pytest
 
-from test_generic_conv_edges_gpu import Edge, _mods, assert_bars
-from test_group16_conv_edges_gpu import plain_dgrad, poison
-from test_lean_conv_edges_gpu import tanh_excess
-from test_small_group_plan_cpu import CASES, MFMA_WGRAD, SG_WGRAD, SPLIT_B, expected_families
+from conv_edge import Edge, plain_dgrad, tanh_excess
+from edge_support import assert_bars, lib, poison_lds
+from small_group_cases import CASES, MFMA_WGRAD, SG_WGRAD, SPLIT_B, small_group_families
 
 pytestmark = pytest.mark.gpu
 
@@ -97,9 +96,9 @@ def run_case(e, name, fams):
 
 @pytest.mark.parametrize('name', list(CASES))
 def test_small_group_edge(name, dev):
-    poison(dev)
+    poison_lds(dev)
     e = make_case(name, dev)
-    fwd, dg, wg = expected_families(name)
+    fwd, dg, wg = small_group_families(name)
     res = run_case(e, name, (fwd, dg, wg))
     if name == 'k3_s4':      # no tap reaches phase 3 of an input position: exact zeros, written (dx started as SENT)
         assert bool((e.dxv[:, :, 3::4] == 0).all()) and bool((e.dxv[:, :, 0::4] != 0).any())
@@ -127,7 +126,7 @@ def test_wgrad_sample_split(B, with_db, dev):
     fourth sample, 2 + 2 + 2 + 2 (B = 8), 3 + 3 + 2 + 2 (10) and 3 + 3 + 3 + 2 (11) of them: the last prefetch of each is guarded by
     b + nsplit < B. Edge's bound scales with B (n = B * Tout)."""
     assert B in SPLIT_B
-    poison(dev)
+    poison_lds(dev)
     e = make_case('tile64', dev, B=B, with_db=with_db)
     res = e.fwd()
     assert_family(e.names['fwd'], 'small_group_fwd_kernel<4>', f'B={B} fwd')
@@ -141,15 +140,14 @@ def test_wgrad_sample_split(B, with_db, dev):
 
 def test_small_group_off_switch(dev):
     """tdvc_debug_knob(2, 1): the same geometry on the generic kernels, same bars."""
-    L = _mods()[1]
-    poison(dev)
+    poison_lds(dev)
     e = make_case('tile64', dev)
-    L.lib().tdvc_debug_knob(2, 1)
+    lib().tdvc_debug_knob(2, 1)
     try:
         res = run_case(e, 'tile64 off', ('conv_gemm_kernel<1,', 'conv_gemm_kernel<2,', MFMA_WGRAD))
         res.update(e.wgrad())
     finally:
-        L.lib().tdvc_debug_knob(2, 0)
+        lib().tdvc_debug_knob(2, 0)
     assert_family(e.names['wgrad'], MFMA_WGRAD, 'tile64 off wgrad')
     assert_bars(res, 'small-group tile64, route switched off')
 
@@ -157,7 +155,7 @@ def test_small_group_off_switch(dev):
 def test_tanh_allowance_measured_on_scalar_route(dev):
     """The measurement behind TANH_EXCESS_MEASURED, repeated: the `tanh` case on the scalar generic route, which must itself pass
     the y bar with the allowance (twice the recorded figure)."""
-    poison(dev)
+    poison_lds(dev)
     e = make_case('tanh', dev, generic=1)
     res = e.fwd()
     assert_family(e.names['fwd'], 'conv_scalar_kernel<1>', 'tanh scalar fwd')

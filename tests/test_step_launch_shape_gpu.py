@@ -19,23 +19,10 @@ import numpy as np
 import pytest
 import torch
 
-from common import GOLDEN, assert_grads_close, build_models, build_ssl_models, filled_sd, pkg, rel_l2, to_dev, traced
+from common import GOLDEN, assert_grads_close, build_models, build_ssl_models, filled_sd, pkg, rel_l2, to_dev, traced, update_stats
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
-
-
-def update_stats(before, after_got, after_ref, lr):
-    """Agreement of two AdamW updates of one tensor. Early Adam steps are ~ -lr * sign(g) per element, so an element whose
-    gradient is below its own fp32 noise may legitimately land 2*lr apart: report the fraction of such elements and the
-    rel-L2 over the rest."""
-    d_got = (after_got.double().cpu() - before.double()).reshape(-1)
-    d_ref = (after_ref.double() - before.double()).reshape(-1)
-    diff = (d_got - d_ref).abs()
-    flipped = diff > 0.5 * lr
-    ok = ~flipped
-    rel_rest = float((d_got[ok] - d_ref[ok]).norm() / (d_ref[ok].norm() + 1e-30)) if ok.any() else 0.0
-    return float(flipped.double().mean()), rel_rest, float(d_ref.norm())
 
 
 # (config, B, T, batch seeds). The gate compares against the oracle's fp32 CPU autograd, so it sees LeakyReLU kink flips: a

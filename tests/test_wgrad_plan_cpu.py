@@ -8,7 +8,7 @@ import importlib
 
 import pytest
 
-from test_lean_wgrad_edges_gpu import CASES, NARROW, X6
+from wgrad_cases import CASES, NARROW, X6
 
 
 def prefers_ct32(cin):

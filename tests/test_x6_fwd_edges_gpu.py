@@ -3,7 +3,7 @@ conv_x6_weight_planes_kernel (conv_fwd_x6.hip), all through the C ABI (tdvc_conv
 tdvc_conv_x6_weight_planes): the operator layer's gates (_x6_fwd_geometry, sign bits only at T >= 512, .contiguous()) hide most of
 the contract.
 
-Same rules as test_generic_conv_edges_gpu.py, whose helpers this file uses: fp32-valued inputs, a float64 CPU reference on the same
+Same rules as test_generic_conv_edges_gpu.py, with the helpers of edge_support.py: fp32-valued inputs, a float64 CPU reference on the same
 numbers (the slope as float(np.float32(slope))), outputs that start as SENT and may be channel slices of wider buffers whose spare
 channels stay SENT, inputs that may be channel slices of [B, C + 4, T] buffers whose spare channels are NaN (a masked-off channel
 >= Cin read as a value turns the output NaN), the weight planes exactly tdvc_conv_x6_weight_planes_bytes inside a guarded buffer.
@@ -15,7 +15,7 @@ NaN-poisoned LDS.
    |cv_ref| <= its bound, element by element.
 2. One product per output element: the bar on the x6 arithmetic itself, |got - ref| <= 2^-20 |ref| (test_x6_split_cpu.py has the
    derivation and asserts its figures). At dense shapes neither bar of part 1 notices a missing lo.hi product.
-3. The weight-plane image, decoded with test_x6_split_cpu.plane_offsets.
+3. The weight-plane image, decoded with x6_split.plane_offsets.
 4. Refusals: the return code, an empty trace, outputs and guards still SENT; built on buffers large enough for the refused geometry.
 """
 import ctypes as C
@@ -26,18 +26,18 @@ import torch
 import torch.nn.functional as F
 
 from common import rel_l2, traced
-from test_film_cond_bwd_edges_gpu import pack_sign_bits
-from test_generic_conv_edges_gpu import SENT, U, Edge, _buf, _mods, _spare_intact, assert_bars, elem_check
-from test_x6_split_cpu import ONE_PRODUCT_BOUND, PLANE_GEOM, constructed, decode_planes, planes_bytes, split3
+from conv_edge import Edge
+from edge_support import (EINVAL, EUNSUPPORTED, SENT, U, Worst, _buf, _spare_intact, assert_bars, elem_check, mods, pack_sign_bits, poison_lds,
+                          stream)
+from x6_split import ONE_PRODUCT_BOUND, PLANE_GEOM, constructed, decode_planes, planes_bytes, split3
 
 pytestmark = pytest.mark.gpu
 
 NV = 8
-EINVAL, EUNSUPPORTED = -1, -4
 GUARD16 = 0x5A5A                         # fills the int16 buffer around a plane image
 BITS_SENT = 0x5A5A5A5A                   # fills a sign-word buffer before the call
 SPECIALS = [0.0, -0.0, 2.0 ** -126]      # +0, -0, the smallest normal
-WORST = {}                               # kernel -> tensor -> (err / bound, case)
+WORST = Worst()                          # kernel -> tensor -> (err / bound, case)
 _DATA = {}                               # case -> inputs and float64 references, computed once and never modified
 
 # name, (Cin, Cout, T, B), options: slope (absent = no prologue), bias=False, views=True (x a slice of a NaN-padded buffer, y a slice of
@@ -84,10 +84,6 @@ PLAIN_BASE = ('plain_refusal_base', (136, 64, 160, 3), dict(slope=0.2, views=Tru
 FUSED_BASE = ('fused_refusal_base', (136, 64, 160, 3), dict(bits=True, views=True))
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _f32(slope):
     return float(np.float32(slope))
 
@@ -116,27 +112,16 @@ def _nan_in(src, dev, view, extra=4):
 
 def make_planes(w_dev, Cout, Cin, dev):
     """tdvc_conv_x6_weight_planes into exactly the queried bytes of a GUARD16-filled int16 buffer -> (whole buffer, the image)."""
-    L = _mods()[1]
+    L = mods()[1]
     lib = L.lib()
     nbytes = lib.tdvc_conv_x6_weight_planes_bytes(Cout, Cin, 3)
     assert nbytes == planes_bytes(Cout), (nbytes, planes_bytes(Cout))
     lead, n = 128, nbytes // 2           # 256 bytes in front: the image stays 256-byte aligned
     whole = torch.full((lead + n + 128,), GUARD16, dtype=torch.int16, device=dev)
-    L.check(lib.tdvc_conv_x6_weight_planes(w_dev.data_ptr(), Cout, Cin, 3, whole.data_ptr() + 2 * lead, _stream(dev)))
+    L.check(lib.tdvc_conv_x6_weight_planes(w_dev.data_ptr(), Cout, Cin, 3, whole.data_ptr() + 2 * lead, stream(dev)))
     g = whole.cpu()
     assert bool((g[:lead] == GUARD16).all() and (g[lead + n:] == GUARD16).all()), 'the planes kernel wrote outside the queried bytes'
     return whole, whole[lead:lead + n]
-
-
-def _note_worst(kernel, res, case):
-    for k, v in res.items():
-        if v['ratio'] >= WORST.setdefault(kernel, {}).get(k, (-1.0, ''))[0]:
-            WORST[kernel][k] = (v['ratio'], case)
-
-
-def _poison(dev):
-    L = _mods()[1]
-    L.check(L.lib().tdvc_debug_poison_lds(0xFFFFFFFF, _stream(dev)))
 
 
 # ------------------------------------------------------------------------------------------------------------ plain forward
@@ -179,7 +164,7 @@ class FwdEdge:
 
     def call(self, desc=None, args=None, planes='own'):
         """One call -> rc; `desc` / `args` replace fields of the two structs, `planes` the image pointer (the refusal tests)."""
-        L = _mods()[1]
+        L = mods()[1]
         dd = dict(kind=L.CONV, B=self.B, Cin=self.Cin, Cout=self.Cout, Tin=self.T, Tout=self.T, K=3, stride=1, dilation=1, pad=1, groups=1,
                   reflect=0, w_cin=0, w_cin_off=0)
         dd.update(desc or {})
@@ -190,19 +175,19 @@ class FwdEdge:
         aa.update(args or {})
         d_, a_ = L.ConvDesc(**dd), L.ConvFwdArgs(**aa)
         with traced() as tr:
-            rc = L.lib().tdvc_conv_fwd_x6(C.byref(d_), C.byref(a_), self.planes.data_ptr() if isinstance(planes, str) else planes, _stream(self.dev))
+            rc = L.lib().tdvc_conv_fwd_x6(C.byref(d_), C.byref(a_), self.planes.data_ptr() if isinstance(planes, str) else planes, stream(self.dev))
         self.names = tr.names
         return rc
 
     def run(self, tag=''):
         rc = self.call()
-        assert rc == 0, (rc, _mods()[1].lib().tdvc_last_error())
+        assert rc == 0, (rc, mods()[1].lib().tdvc_last_error())
         assert self.names == {self.kernel()}, (self.name, sorted(self.names), self.kernel())
         ratio, inexact = elem_check(self.y, self.d['ref'], self.d['A'], 3 * self.Cin + 1)
         res = dict(y=dict(rel=rel_l2(self.y, self.d['ref']), ratio=ratio, inexact=inexact))
         assert_bars(res, f'{self.kernel()}: {self.name}{tag}')
         assert _spare_intact(self.y_whole, self.Cout), 'wrote into the spare channels behind y'
-        _note_worst(self.kernel(), res, self.name)
+        WORST.note(self.kernel(), res, self.name)
         return res
 
 
@@ -216,7 +201,7 @@ def test_plain_edge(name, dev):
 def test_plain_edge_poisoned_lds(name, dev):
     """Once more on NaN-poisoned LDS: the halo rows of a tile outside the sequence, the masked channels of a partial chunk and the
     weight rows of channels >= Cin must come from the kernel, not from what LDS held."""
-    _poison(dev)
+    poison_lds(dev)
     e = FwdEdge(name, dev)
     e.run(' (poisoned LDS)')
     assert bool(torch.isfinite(e.y).all())
@@ -310,7 +295,7 @@ class CondFwdEdge:
         return f'film_cond_fwd_x6_kernel<{2 if self.C2 % 64 else 4}>'
 
     def call(self, args=None, planes='own', bits='own', bits_bs=None):
-        L = _mods()[1]
+        L = mods()[1]
         aa = dict(B=self.B, T=self.T, n_cond=self.nc, n_var=NV, C2=self.C2, exc=self.exc.data_ptr(), exc_bs=self.exc.stride(0), w0=self.w0.data_ptr(),
                   k3=self.k3.data_ptr(), w2=None, b2=self.b2.data_ptr() if self.b2 is not None else None,
                   cv0=self.cv0.data_ptr() if self.cv0 is not None else None, cv0_bs=self.cv0.stride(0) if self.cv0 is not None else 0,
@@ -322,7 +307,7 @@ class CondFwdEdge:
         if bits_bs is None:
             bits_bs = self.bits.stride(0) if self.bits is not None else 0
         with traced() as tr:
-            rc = L.lib().tdvc_film_cond_fwd_x6(C.byref(a_), self.planes.data_ptr() if isinstance(planes, str) else planes, bits, bits_bs, _stream(self.dev))
+            rc = L.lib().tdvc_film_cond_fwd_x6(C.byref(a_), self.planes.data_ptr() if isinstance(planes, str) else planes, bits, bits_bs, stream(self.dev))
         self.names = tr.names
         return rc
 
@@ -333,7 +318,7 @@ class CondFwdEdge:
 
     def run(self, tag=''):
         rc = self.call()
-        assert rc == 0, (rc, _mods()[1].lib().tdvc_last_error())
+        assert rc == 0, (rc, mods()[1].lib().tdvc_last_error())
         assert self.names == {self.kernel()}, (self.name, sorted(self.names), self.kernel())
         d, res = self.d, {}
         for k, t in (('gb', self.gb),) + ((('cv0', self.cv0),) if self.cv0 is not None else ()):
@@ -359,7 +344,7 @@ class CondFwdEdge:
             assert bool((self.cv0[b].view(torch.int32) == 0).all()), 'cv0 of the zero sample is not +0'
             assert bool((self.bits[b] == 0).all()), 'sign bits of the zero sample'
             assert torch.equal(self.gb[b].cpu(), d['b2'][:, None].expand(self.C2, self.T)), 'gb of the zero sample is not b2 bit for bit'
-        _note_worst(self.kernel(), res, self.name)
+        WORST.note(self.kernel(), res, self.name)
         return res
 
 
@@ -373,7 +358,7 @@ def test_fused_edge(name, dev):
 def test_fused_edge_poisoned_lds(name, dev):
     """Once more on NaN-poisoned LDS: the excitation window's columns outside the sequence, the activation rows of channels >= n_cond
     and the halo rows of an edge tile must come from the kernel."""
-    _poison(dev)
+    poison_lds(dev)
     e = CondFwdEdge(name, dev)
     e.run(' (poisoned LDS)')
     assert bool(torch.isfinite(e.gb).all())
@@ -424,7 +409,7 @@ def test_one_product_forward(Cin, Cout, dev):
     row = ('one_product', (Cin, Cout, T, B), dict(bias=False))
     for tag in ('', ' (poisoned LDS)'):
         if tag:
-            _poison(dev)
+            poison_lds(dev)
         e = FwdEdge(f'one_product_{Cin}_{Cout}', dev, row=row, data=dict(x=x, W=W, bias=None))
         assert e.call() == 0 and e.names == {e.kernel()}
         _one_product_check(e.y, ref, f'{e.kernel()} {Cin} -> {Cout}{tag}')
@@ -457,7 +442,7 @@ def test_one_product_fused(draw, dev):
     row = ('one_product_fused', (nc, C2, T, B), dict(b2=False))
     for tag in ('', ' (poisoned LDS)'):
         if tag:
-            _poison(dev)
+            poison_lds(dev)
         e = CondFwdEdge(f'one_product_fused_{draw}', dev, row=row, data=data)
         assert e.call() == 0 and e.names == {e.kernel()}
         ref = F.conv1d(_lrelu64(e.cv0.cpu().double(), 0.2), data['W2'].double(), padding=1)
@@ -480,7 +465,7 @@ def test_one_product_weight_grad(dev):
     e = Edge(('x6_one_product', Cin, Cout, 3, 1, 1, 1, 1, False, False, 0, T), dev, B=1, with_db=False)
     e.xv.copy_(x.to(dev)); e.dyv.copy_(dy.to(dev)); e.dw.zero_()
     rc = e.wgrad_call()
-    assert rc == 0 and e.guard_ok, (rc, _mods()[1].lib().tdvc_last_error())
+    assert rc == 0 and e.guard_ok, (rc, mods()[1].lib().tdvc_last_error())
     assert e.names['wgrad'] == {'conv_wgrad_x6_kernel', 'slab_reduce_multi_kernel'}, sorted(e.names['wgrad'])
     assert int((ref == 0).sum()) == 2 * Cin      # tap 0 of the channel at t = 0, tap 2 of the channel at t = T - 1
     _one_product_check(e.dw, ref, 'conv_wgrad_x6_kernel 136 -> 32')
@@ -509,20 +494,20 @@ def test_weight_plane_image(Cout, Cin, dev):
 
 def test_weight_planes_refuse_partial_record(dev):
     """Cout % 32 != 0: no kernel could read a partial record. TDVC_EINVAL and a buffer (large enough for the next multiple) untouched."""
-    L = _mods()[1]
+    L = mods()[1]
     lib = L.lib()
     w = torch.randn(64, 136, 3, device=dev)
     buf = torch.full((planes_bytes(64) // 2,), GUARD16, dtype=torch.int16, device=dev)
     for Cout in (48, 16):
         assert lib.tdvc_conv_x6_weight_planes_bytes(Cout, 136, 3) == 0
-        assert lib.tdvc_conv_x6_weight_planes(w.data_ptr(), Cout, 136, 3, buf.data_ptr(), _stream(dev)) == EINVAL
+        assert lib.tdvc_conv_x6_weight_planes(w.data_ptr(), Cout, 136, 3, buf.data_ptr(), stream(dev)) == EINVAL
     torch.cuda.synchronize()
     assert bool((buf == GUARD16).all())
 
 
 # ------------------------------------------------------------------------------------------------------- refusals (part 4)
 def _xf(kind, slope, scale=1.0, aux=None):
-    return _mods()[1].Xform(kind, slope, scale, aux.data_ptr() if aux is not None else None, aux.stride(0) if aux is not None else 0)
+    return mods()[1].Xform(kind, slope, scale, aux.data_ptr() if aux is not None else None, aux.stride(0) if aux is not None else 0)
 
 
 KNOBS = {'knob6': (lambda lib: lib.tdvc_debug_knob(6, 1), lambda lib: lib.tdvc_debug_knob(6, 0)),
@@ -562,7 +547,7 @@ def _planes_off(e, poff):
 
 
 def _with_knob(what, fn):
-    lib = _mods()[1].lib()
+    lib = mods()[1].lib()
     if what not in KNOBS:
         return fn()
     KNOBS[what][0](lib)
@@ -580,7 +565,7 @@ def test_plain_refusals(what, dev):
     e = FwdEdge(PLAIN_BASE[0], dev)
     rc = _with_knob(what, lambda: e.call(desc, args(e) if callable(args) else args, _planes_off(e, poff)))
     torch.cuda.synchronize()
-    assert rc == code, (what, rc, _mods()[1].lib().tdvc_last_error())
+    assert rc == code, (what, rc, mods()[1].lib().tdvc_last_error())
     assert not e.names, sorted(e.names)
     assert bool((e.y_whole == SENT).all()), 'a refused call wrote y'
     if what == 'Cin64':      # the base call itself is inside the contract
@@ -623,7 +608,7 @@ def test_fused_refusals(what, dev):
     e.bits = e.bits_whole[:, :e.nc]
     rc = _with_knob(what, lambda: e.call(args(e) if callable(args) else args, _planes_off(e, poff)))
     torch.cuda.synchronize()
-    assert rc == code, (what, rc, _mods()[1].lib().tdvc_last_error())
+    assert rc == code, (what, rc, mods()[1].lib().tdvc_last_error())
     assert not e.names, sorted(e.names)
     assert e.untouched(), 'a refused call wrote an output'
     if what == 'n_var4':      # the base call itself is inside the contract
@@ -632,5 +617,4 @@ def test_fused_refusals(what, dev):
 
 def test_zz_worst_error_by_kernel():
     """Prints the worst err / bound per kernel and tensor over the cases that ran in this session (asserted case by case)."""
-    for kernel, per in sorted(WORST.items()):
-        print(f'[edge] worst {kernel}: ' + '  '.join(f'{k} {r:.3f} ({n})' for k, (r, n) in sorted(per.items())))
+    WORST.report()

@@ -1,5 +1,5 @@
-"""The split-bf16 x6 scheme of csrc/split_bf16.h restated in numpy, and the figures the one-product bar of test_x6_fwd_edges_gpu.py
-rests on. No GPU: the split is three truncations and two exact subtractions, a piece product is exact in fp32 (8 x 8 significant
+"""The figures the one-product bar of test_x6_fwd_edges_gpu.py rests on, from the split-bf16 x6 scheme of csrc/split_bf16.h as x6_split.py
+restates it in numpy. No GPU: the split is three truncations and two exact subtractions, a piece product is exact in fp32 (8 x 8 significant
 bits), and with ONE nonzero product per output element the matrix pipe's accumulation is six fp32 additions in the committed order.
 
 Operands of the one-product rows are s * 2^e * (h 2^16 + m 2^8 + l) * 2^-23 with h, m, l in [128, 255]: every piece is exactly
@@ -9,31 +9,19 @@ them out is far outside
 while the full scheme stays below 8.1 * 2^-24: the three dropped products are below (2^-23 + 2^-32) |w x| and six additions round
 by at most 6 * 2^-24. Both figures are asserted here, on 2e5 pairs.
 
-Also here: the index function of the weight-plane image (tdvc_conv_x6_weight_planes) that the GPU file decodes the planes with,
-and the byte count of that image against the host library.
+Also here: the index function of the weight-plane image (tdvc_conv_x6_weight_planes; x6_split.plane_offsets, which the GPU file decodes
+the planes with) is checked, and the byte count of that image against the host library.
 """
 import importlib
 
 import numpy as np
 import pytest
 
-F32, U32 = np.float32, np.uint32
+from x6_split import F32, ONE_PRODUCT_BOUND, PLANE_GEOM, U32, constructed, plane_offsets, planes_bytes, split3, x6_mt
+
 # (weight piece, activation piece) in the order x6_mfma issues them: smallest products first. 0 = hi, 1 = mid, 2 = lo
 ORDER = [(2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0)]
 PRODUCT_NAMES = ['lo.hi', 'hi.lo', 'mid.mid', 'mid.hi', 'hi.mid', 'hi.hi']
-X6_CP = 160                              # padded input-channel count of the plane image: 5 chunks of 32
-ONE_PRODUCT_BOUND = 2.0 ** -20
-
-
-def split3(x):
-    """x6_split: x = hi + mid + lo exactly, each piece the upper 16 bits of its fp32 word (a bf16 value)."""
-    x = np.ascontiguousarray(x, dtype=F32)
-    top = lambda v: (v.view(U32) & U32(0xffff0000)).view(F32)
-    h = top(x)
-    r1 = (x - h).astype(F32)
-    m = top(r1)
-    r2 = (r1 - m).astype(F32)
-    return h, m, top(r2)                 # lo's lower half is zero by construction; the pack drops it
 
 
 def x6_product(w, x, omit=None):
@@ -44,43 +32,6 @@ def x6_product(w, x, omit=None):
         if k != omit:
             c = (c + pw[i] * px[j]).astype(F32)      # the product has 16 significant bits: exact in fp32
     return c
-
-
-def constructed(rng, shape):
-    """-> (fp32 values s 2^e (h 2^16 + m 2^8 + l) 2^-23, h, m, l, e, s) with h, m, l in [128, 255], e in [-20, 20]."""
-    h, m, l = (rng.integers(128, 256, size=shape) for _ in range(3))
-    e = rng.integers(-20, 21, size=shape)
-    s = rng.choice(np.array([-1.0, 1.0]), size=shape)
-    v = s * (h * 65536.0 + m * 256.0 + l) * 2.0 ** (e - 23.0)
-    assert np.array_equal(v.astype(F32).astype(np.float64), v)
-    return v.astype(F32), h, m, l, e, s
-
-
-def x6_mt(Cout):
-    return 64 if Cout % 64 == 0 else 32
-
-
-def planes_bytes(Cout):
-    """Bytes of the plane image: three pieces x Cout x 3 taps x 160 padded channels, bf16."""
-    return 3 * Cout * 3 * X6_CP * 2
-
-
-def plane_offsets(Cout):
-    """Element offset of (piece, co, tap, ci) in the image [Cout / MT][5 chunks][MT / 32][piece][32 co][tap][32 ci] -> int64
-    array [3][Cout][3][160]. MT = 64 iff Cout % 64 == 0: the 32-channel chunk of one block's MT output channels is one linear run."""
-    assert Cout % 32 == 0
-    cbn = x6_mt(Cout) // 32
-    pc, co, j, ci = np.ix_(np.arange(3), np.arange(Cout), np.arange(3), np.arange(X6_CP))
-    blk, cb, co32 = co // (32 * cbn), (co // 32) % cbn, co % 32
-    rec = (blk * 5 + ci // 32) * cbn + cb
-    return (((rec * 3 + pc) * 32 + co32) * 3 + j) * 32 + ci % 32
-
-
-def decode_planes(words, Cout):
-    """uint16 image -> fp32 pieces [3][Cout][3][160]."""
-    words = np.ascontiguousarray(words).view(np.uint16)
-    assert words.size == planes_bytes(Cout) // 2
-    return (words[plane_offsets(Cout)].astype(U32) << U32(16)).view(F32)
 
 
 N_PAIRS = 200_000
@@ -125,9 +76,6 @@ def test_one_product_figures(pairs):
         r = rel(x6_product(w, x, omit=k))
         print(f'[x6 split] without {name}: least {r.min() / 2.0 ** -20:.2f} * 2^-20')
         assert r.min() >= 2.0 ** -18 > 3.9 * ONE_PRODUCT_BOUND
-
-
-PLANE_GEOM = [(32, 65), (64, 136), (96, 100), (128, 72), (160, 160)]
 
 
 @pytest.mark.parametrize('Cout,Cin', PLANE_GEOM + [(256, 136)])
