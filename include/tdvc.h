@@ -719,6 +719,94 @@ int tdvc_lstm_fwd(const float* frames, int64_t f_bs, int64_t f_fs, int32_t B, in
 int tdvc_voice_embed(const float* h, int32_t B, int32_t P_max, const int32_t* counts, const float* W, const float* bias,
                      float* partial, float* utt, void* stream);
 
+/* Speaker recognition (csrc/eval_ecapa.hip): speechbrain's Fbank + sentence mean normalisation + ECAPA-TDNN embedding, the path of
+ * the reference's test_scripts/mls-pt/test_speaker_rec.py (lines 58-186; the vctk script is wired the same way), restated here from
+ * knowledge of speechbrain 0.5's lobes/features.py, processing/features.py, nnet/CNN.py and lobes/models/ECAPA_TDNN.py. Neither
+ * speechbrain nor torchaudio is available and the reference ships no embedding_model.ckpt: this definition is the contract and
+ * tests/ecapa_ref.py restates it in float64; PARITY WITH AN INSTALLED SPEECHBRAIN IS UNCHECKED, and so are the state-dict keys
+ * against a real embedding_model.ckpt. Every quirk below is speechbrain's and is kept.
+ *   Input: a 16 kHz waveform row of n samples; samples at and past n are never read and count as zero.
+ *   Features (Fbank(n_mels=80), InputNormalization(norm_type='sentence', std_norm=False)):
+ *     STFT: n_fft = win = 400, hop 160, periodic Hamming window (torch.hamming_window(400): 0.54 - 0.46 cos(2 pi i / 400)),
+ *       center=True with pad_mode='constant' (zeros), one-sided 201 bins; frame count F = 1 + n / 160 (integer division).
+ *     Power: re^2 + im^2 (spectral_magnitude(power=1) returns the power spectrum, not its root).
+ *     Filterbank: HTK mel scale mel = 2595 log10(1 + hz/700); hz[0..n_mels+1] the image of n_mels + 2 points equally spaced in mel on
+ *       0..8000 Hz; f_c[i] = hz[i+1]; band[i] = hz[i+1] - hz[i] (THE LEFT WIDTH ONLY); bin frequencies linspace(0, 8000, 201); filter
+ *       i at bin frequency f is max(0, min((f - f_c[i])/band[i] + 1, -(f - f_c[i])/band[i] + 1)): a symmetric triangle of half-width
+ *       band[i] with peak 1, no area normalisation.
+ *     dB: 10 log10(max(x, 1e-10)), then max(., M - 80) with M the largest dB value of the row over its own F frames and all bands.
+ *     Normalisation: subtract, per band, the mean over the row's F frames.
+ *   Network (ECAPA_TDNN(input_size=80, channels=[C,C,C,C,3C] = [1024,1024,1024,1024,3072], kernel_sizes=[5,3,3,3,1],
+ *   dilations=[1,2,3,4,1], attention_channels=128, lin_neurons=192), res2net_scale=8, se_channels=128, global_context=True, eval):
+ *     Conv1d: "same"-padded with REFLECT padding, (k - 1) d / 2 per side, the edge sample not repeated, about the ROW'S OWN first and
+ *       last frame (not the buffer's). TDNNBlock(x) = BatchNorm(ReLU(conv(x))), running statistics, eps 1e-5.
+ *     blocks[0] = TDNNBlock(80 -> C, k5, d1). blocks[1..3] = SERes2NetBlock(C -> C, k3, d = 2, 3, 4): tdnn1 (k1); Res2Net over 8 channel
+ *       chunks, y0 = x0, y1 = B0(x1), yi = B(i-1)(xi + y(i-1)), each B a TDNNBlock(C/8 -> C/8, k3, d); tdnn2 (k1); SE: s = mean over the
+ *       row's frames, g = sigmoid(conv2(relu(conv1(s)))), g x; then + the block's input.
+ *     MFA: x = cat(blocks[1..3] outputs) -> mfa = TDNNBlock(3C -> 3C, k1).
+ *     Attentive statistics pooling over the row's frames: uniform-weight mean m and sd = sqrt(clamp(sum w (x - m)^2, 1e-12));
+ *       a = conv(tanh(TDNNBlock_{9C -> A, k1}(cat[x, m, sd]))); softmax over the row's frames; weighted m, sd by the same formula -> [6C].
+ *     Head: asp_bn -> fc (1x1 conv 6C -> lin_neurons) -> the embedding.
+ *   Classifier(192, S): logits = normalize(e) normalize(weight)^T; the script takes softmax over S, the argmax and the target's
+ *   probability, and subtracts from the k-th embedding the running mean of embeddings 1..k (mean_var_norm_emb is never put in eval
+ *   mode): both are stock torch ops in td-vc-gan_amd/ecapa.py (speaker_classify, running_mean_norm).
+ *   Stated deviations and limits: a row is evaluated as if alone (the reference passes one file with lengths = [1.0]); rows of fewer
+ *   than 5 frames (n < 640) are refused: a reflect pad of 4 needs 5 frames (T < 640 on the host; a DEVICE length below 640 cannot be
+ *   refused without a synchronisation: such a row's result is unspecified, its indices are clamped into the row); every channel count
+ *   a multiple of 16 (and C of 128, so that C/8 is); inference only; the vctk script's 48 kHz resampling of a 16 kHz file is not
+ *   reproduced.
+ * Activations are fp32 [B][C][F] at p[b bs + c cs + f] (dense frames), so that channel slices of wider buffers work. `frames` is
+ * device int32 [B] (written by tdvc_fbank) or NULL for full rows; it is clamped to [0, F]. Frames at and past a row's count are never
+ * read, and never written except by tdvc_fbank, which writes them as zeros. No host synchronisation, no atomics, fixed summation
+ * orders: bit-identical from call to call, a row's result does not depend on its batch; graph-capturable.
+ * tdvc_fbank: signal [B] rows of T samples (row stride s_bs), lengths device int32 [B] or NULL -> feats [B][n_mels][F], F = 1 + T/160,
+ *   and frames[b] = 1 + n_b/160. tables: float64 [400 cos(2 pi i/400) | 400 sin | 400 Hamming | n_mels x 201 filterbank], built on the
+ *   host. Float64 inside, one rounding at the store; two passes (dB values and per-block maxima into the workspace; row maximum,
+ *   floor, mean), both in fixed orders.
+ * tdvc_tdnn_fwd: y = epilogue(conv(x [+ x2]) + bias [+ row_bias[b]]), w [Cout][Cin][K] with row stride w_rs (0: Cin K; larger: the
+ *   first Cin K columns of wider rows), K in {1, 3, 5}, dilation 1..4; epilogue 0: none; 1: ReLU then v scale[co] + shift[co] (the
+ *   folded BatchNorm: scale = gamma / sqrt(var + eps), shift = beta - mean scale); 2: that followed by tanh. x2: an optional second
+ *   input added to x before the convolution; row_bias: optional [B][Cout]. y must not overlap x or x2. An implicit GEMM on
+ *   v_mfma_f32_16x16x4_f32 (exact fp32): 64 output channels x 64 frames per workgroup, chunks of 32 (K = 1) or 16 input channels summed from zero
+ *   and then accumulated.
+ * tdvc_se_block: s = mean of x over the row's frames, g = sigmoid(w2 relu(w1 s + b1) + b2) (w1 [S][C], w2 [C][S]), out = g x +
+ *   residual; gate: fp32 [B][C + S], scratch and output (the gates in the first C floats of a row, the hidden layer behind them).
+ *   Four launches.
+ * tdvc_asp_pool: x [B][C][F] -> pooled [B][2C] = (weighted mean | weighted sd); w_tdnn [A][3C] with bias and folded scale / shift [A],
+ *   w_conv [C][A] with bias [C]. The columns C..3C of w_tdnn meet inputs that are constant over time: they become a per-row bias.
+ * tdvc_ecapa_head: emb[b][e] = sum_j w[e][j] (pooled[b][j] scale[j] + shift[j]) + bias[e], w [E][N].
+ * The statistics, matrix-vector products, softmax and head accumulate in float64 and round once.
+ * TDVC_EINVAL: negative sizes or strides, null pointers, an epilogue outside 0..2, F != 1 + T/160, w_rs < Cin K or not a multiple of 4,
+ * convolution weights that are not 16-byte aligned (the kernel loads them as float4). TDVC_EUNSUPPORTED: a channel stride above 2^27, T <
+ * 640 or F < 5, a channel count (or n_mels) that is not a multiple of 16, n_mels > 128, K outside {1, 3, 5}, dilation outside 1..4,
+ * C or S > 65532 (se_block), B > 65535, more than 2^20 channels or 2^24 frames, T > 2^26. TDVC_EWORKSPACE for a null or too small
+ * workspace (tdvc_fbank_workspace, tdvc_asp_pool_workspace: 0 on arguments the call refuses). All before any launch; B == 0 is a
+ * no-op. */
+typedef struct {
+  int32_t B, Cin, Cout, F, K, dilation, epilogue, reserved;
+  const float* x; int64_t x_bs, x_cs;
+  const float* x2; int64_t x2_bs, x2_cs;      /* NULL: no second input */
+  const float* w; int64_t w_rs;
+  const float* bias;                          /* [Cout] or NULL */
+  const float* row_bias;                      /* [B][Cout] or NULL */
+  const float* scale; const float* shift;     /* [Cout], epilogue 1 and 2 */
+  float* y; int64_t y_bs, y_cs;
+  const int32_t* frames;                      /* device [B] or NULL */
+} tdvc_tdnn_args;
+size_t tdvc_fbank_workspace(int32_t B, int32_t T, int32_t n_mels);
+int tdvc_fbank(const float* signal, int64_t s_bs, const int32_t* lengths, int32_t T, int32_t B, int32_t n_mels, const double* tables,
+               float* feats, int64_t f_bs, int64_t f_cs, int32_t F, int32_t* frames, void* workspace, size_t workspace_bytes, void* stream);
+int tdvc_tdnn_fwd(const tdvc_tdnn_args* args, void* stream);
+int tdvc_se_block(const float* x, int64_t x_bs, int64_t x_cs, const float* residual, int64_t r_bs, int64_t r_cs, int32_t B, int32_t C,
+                  int32_t F, const int32_t* frames, int32_t S, const float* w1, const float* b1, const float* w2, const float* b2,
+                  float* gate, float* out, int64_t o_bs, int64_t o_cs, void* stream);
+size_t tdvc_asp_pool_workspace(int32_t B, int32_t C, int32_t A, int32_t F);
+int tdvc_asp_pool(const float* x, int64_t x_bs, int64_t x_cs, int32_t B, int32_t C, int32_t F, const int32_t* frames, int32_t A,
+                  const float* w_tdnn, const float* b_tdnn, const float* scale, const float* shift, const float* w_conv,
+                  const float* b_conv, float* pooled, void* workspace, size_t workspace_bytes, void* stream);
+int tdvc_ecapa_head(const float* pooled, int32_t B, int32_t N, const float* scale, const float* shift, const float* w, const float* bias,
+                    int32_t E, float* emb, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

@@ -11,7 +11,9 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     and WORLD's DIO + StoneMask F0 as dio / stonemask / world_f0 (pitch.py; mcd(f0_method='dio')), and the speaker-similarity
     evaluation of test_scripts/common/test_speaker_rec.py (Resemblyzer's VoiceEncoder.embed_utterance, per-speaker centroids, cosine
     similarity and nearest-centroid accuracy) as VoiceEncoder / load_voice_encoder / voice_mel / lstm_fwd / partial_slices /
-    window_count / speaker_similarity (speaker.py).
+    window_count / speaker_similarity (speaker.py), and the speechbrain speaker recognition of
+    test_scripts/mls-pt/test_speaker_rec.py (Fbank features, the ECAPA-TDNN embedding, the cosine classifier) as EcapaTdnn /
+    load_ecapa / fbank / fbank_matrix / speaker_classify / running_mean_norm (ecapa.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -26,7 +28,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -40,6 +42,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.evaluate'), name)
     if name in ('VoiceEncoder', 'load_voice_encoder', 'voice_mel', 'lstm_fwd', 'partial_slices', 'window_count', 'speaker_similarity'):
         return getattr(importlib.import_module(f'{__name__}.speaker'), name)
+    if name in ('EcapaTdnn', 'load_ecapa', 'fbank', 'fbank_matrix', 'speaker_classify', 'running_mean_norm'):
+        return getattr(importlib.import_module(f'{__name__}.ecapa'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

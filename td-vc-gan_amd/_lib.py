@@ -70,6 +70,14 @@ class ConvDgradArgs(C.Structure):
                 ('dx', C.c_void_p), ('dx_bs', C.c_int64), ('x_sign_bits', C.c_void_p), ('x_sign_bits_bs', C.c_int64)]
 
 
+class TdnnArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('F', C.c_int32), ('K', C.c_int32), ('dilation', C.c_int32),
+                ('epilogue', C.c_int32), ('reserved', C.c_int32), ('x', C.c_void_p), ('x_bs', C.c_int64), ('x_cs', C.c_int64),
+                ('x2', C.c_void_p), ('x2_bs', C.c_int64), ('x2_cs', C.c_int64), ('w', C.c_void_p), ('w_rs', C.c_int64),
+                ('bias', C.c_void_p), ('row_bias', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p),
+                ('y', C.c_void_p), ('y_bs', C.c_int64), ('y_cs', C.c_int64), ('frames', C.c_void_p)]
+
+
 class L1Pair(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('da', C.c_void_p), ('n', C.c_int64), ('weight', C.c_float)]
 
@@ -86,6 +94,7 @@ CONV, CONV_TRANSPOSE = 0, 1
 POST_NONE, POST_LRELU, POST_TANH = 0, 1, 2
 DG_PLAIN, DG_MASK_LRELU, DG_FILM = 0, 1, 2
 DTW_L2, DTW_L1, DTW_SQ = 0, 1, 2      # tdvc_dtw metric (include/tdvc.h)
+TDNN_NONE, TDNN_RELU_BN, TDNN_RELU_BN_TANH = 0, 1, 2      # tdvc_tdnn_fwd epilogue (include/tdvc.h)
 RESAMPLE_TO = 256      # outputs per block of tdvc_resample (= tdvc_resample_tile(), csrc/audio_resample.hip RS_TO)
 
 # name -> (restype, argtypes); every symbol include/tdvc.h declares
@@ -198,6 +207,15 @@ SIGNATURES = {
     'tdvc_lstm_fwd': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                            C.POINTER(C.c_void_p), _vp, _vp, C.c_size_t, _vp]),
     'tdvc_voice_embed': (_i, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'tdvc_fbank_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_fbank': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _i64, _i64, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    'tdvc_tdnn_fwd': (_i, [C.POINTER(TdnnArgs), _vp]),
+    'tdvc_se_block': (_i, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _i64, _i64, _vp]),
+    'tdvc_asp_pool_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_asp_pool': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           C.c_size_t, _vp]),
+    'tdvc_ecapa_head': (_i, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),
