@@ -503,8 +503,9 @@ __device__ LossAcc g_loss_acc[LOSS_SITES];
 __device__ __forceinline__ void loss_accumulate(float* out, float v, int site) {      // one thread per block calls this
   LossAcc* a = &g_loss_acc[site];
   const unsigned int nblocks = gridDim.x * gridDim.y * gridDim.z;
-  if (fabsf(v) < 1048576.f) atomicAdd(&a->sum, (unsigned long long)__double2ll_rn((double)v * 1099511627776.0));
-  else atomicAdd(out, v);                                                            // also NaN: the comparison is false
+  // |v| < 2^20, and |v| * nblocks < 2^22 so that the sum over all the blocks of the launch stays inside the signed 64 bits (< 2^62 * 2^-40)
+  if (fabsf(v) < 1048576.f && fabsf(v) * (float)nblocks < 4194304.f) atomicAdd(&a->sum, (unsigned long long)__double2ll_rn((double)v * 1099511627776.0));
+  else atomicAdd(out, v);                                                            // also NaN: the comparisons are false
   __threadfence();
   if (atomicAdd(&a->arrived, 1u) == nblocks - 1) {
     __threadfence();

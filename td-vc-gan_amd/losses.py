@@ -121,6 +121,22 @@ def _group(views):
     return tensors, which
 
 
+def _refuse_bad_ranges(fn, tensors, which, ranges):
+    """ValueError, before anything is launched, if one of the sample ranges (off, n) of tensor which[i] is empty or two ranges of
+    one tensor overlap. The backward kernels WRITE each range's gradient, they do not add: overlapping ranges would keep only the
+    gradient of the one launched last; an empty range divides its weight by an element count of 0 (NaN)."""
+    seen = {}
+    for ti, (off, n) in zip(which, ranges):
+        if n <= 0 or tensors[ti].numel() == 0:
+            raise ValueError(f'{fn}: empty sample range [{off}, {off + n}) of a tensor of shape {tuple(tensors[ti].shape)}')
+        seen.setdefault(ti, []).append((off, off + n))
+    for ti, rs in seen.items():
+        rs.sort()
+        for (lo0, hi0), (lo1, hi1) in zip(rs, rs[1:]):
+            if lo1 < hi0:
+                raise ValueError(f'{fn}: sample ranges [{lo0}, {hi0}) and [{lo1}, {hi1}) of one tensor overlap')
+
+
 def _fill_gaps(dx, ranges, lib):
     """Zero the rows of dx that none of the (off, n) ranges covers."""
     per = dx[0].numel()
@@ -176,6 +192,7 @@ def lsgan_loss(outs, target, rng=None):
     if rng is not None:
         views = [v.rows(int(rng[0]), int(rng[1])) for v in views]
     tensors, which = _group(views)
+    _refuse_bad_ranges('lsgan_loss', tensors, which, [(v.off, v.n) for v in views])
     spec = [(ti, v.off, v.n, float(target), 0) for ti, v in zip(which, views)]
     return MseViewsFn.apply(spec, 1, *tensors)[0]
 
@@ -185,6 +202,9 @@ def lsgan_split(outs, B):
     (sum_i mean((o_i[:B] - 1)^2), sum_i mean(o_i[B:]^2))."""
     views = [as_view(o) for o in outs]
     tensors, which = _group(views)
+    B = int(B)
+    _refuse_bad_ranges('lsgan_split', tensors, [ti for ti in which for _ in range(2)],
+                       [r for v in views for r in ((v.off, B), (v.off + B, v.n - B))])
     spec = []
     for ti, v in zip(which, views):
         spec.append((ti, v.off, B, 1.0, 0))
@@ -249,6 +269,7 @@ def multiscale_feat_loss(feat_sig_list, feat_ref_list, norm_p=1, rng=None):
             raise RuntimeError(f'l1 pair batch mismatch {v.n} vs {w.n}')
     ta, wa = _group(a)
     tb, wb = _group(b)
+    _refuse_bad_ranges('multiscale_feat_loss', ta, wa, [(v.off, v.n) for v in a])
     spec = [(ia, v.off, v.n, ib, w.off) for ia, v, ib, w in zip(wa, a, wb, b)]
     return L1ViewsFn.apply(spec, len(ta), *ta, *tb)
 

@@ -16,10 +16,10 @@ def f0_to_excitation(f0, step_size, sampling_rate=16000, linear=True, noise=None
     the same draw; by default they are drawn on the device with torch's generator.
     """
     H.need_device('f0_to_excitation', f0)
+    if f0.dim() != 3 or f0.shape[1] != 1 or f0.shape[2] < 2:
+        raise ValueError(f'f0_to_excitation: f0 must be [B, 1, n_frames >= 2], got {tuple(f0.shape)}')
     f0 = f0.contiguous().float()
-    B, one, nf = f0.shape
-    if one != 1 or nf < 2:
-        raise ValueError('f0 must be [B, 1, n_frames >= 2]')
+    B, _, nf = f0.shape
     T = (nf - 1) * int(step_size)
     dev = f0.device
     if noise is None:
