@@ -807,6 +807,81 @@ int tdvc_asp_pool(const float* x, int64_t x_bs, int64_t x_cs, int32_t B, int32_t
 int tdvc_ecapa_head(const float* pooled, int32_t B, int32_t N, const float* scale, const float* shift, const float* w, const float* bias,
                     int32_t E, float* emb, void* stream);
 
+/* SSL features (csrc/ssl_wavlm.hip): the WavLM feature extractor that the reference's model/ssl_encoder.py:141-145 calls as
+ * WavLM.extract_features(source)[0], from the reference's vendored wavlm/WavLM.py (W) and wavlm/modules.py (M): eval mode,
+ * padding_mask=None, mask=False, the layer-norm feature extractor, layer_norm_first=True, relative position embedding with
+ * gru_rel_pos=True. The reference ships the code but not the 1.2 GB checkpoint: the definition is pinned to the reference's code by a
+ * fixture of its own float64 output on a small seeded configuration (tests/golden/wavlm_small.npz, tools/make_golden_wavlm.py) and
+ * restated in float64 in tests/wavlm_ref.py; PARITY WITH A REAL WAVLM-LARGE.PT IS UNCHECKED (the checkpoint is absent).
+ * WavLM-Large is expected to be 7 convs (512,10,5) + (512,3,2) x 4 + (512,2,2) x 2 without bias, 24 layers of width 1024 with 16
+ * heads and FFN 4096, conv_pos=128, conv_pos_groups=16, num_buckets=320, max_distance=800; the checkpoint's own cfg dict rules.
+ *   1. Input: a waveform row of L samples, used as it is: the reference never applies cfg.normalize (its caller would have to, and
+ *      SSLEncoder does not). Rows are full length: there are NO PER-ROW LENGTHS. A row's result does not depend on its batch.
+ *   2. Front end (W:378-504): per layer Conv1d without bias, LayerNorm over the channels (eps 1e-5, affine), erf-GELU; frame counts
+ *      (L - k) / s + 1 per layer (integer division); a row with no frame (L < 400 for the shipped layers) is refused. Then
+ *      WavLM.layer_norm over the last layer's channels, then post_extract_proj (what ret_conv=True returns).
+ *   3. Positional convolution (W:514-527, 577-580): grouped Conv1d(C, C, K, padding K/2, groups G) with weight norm over dim=2:
+ *      w = g v / ||v||, the norm over dims 0 and 1, one norm per tap; the last output frame is dropped (SamePad of an even K); GELU;
+ *      x = x + pos.
+ *   4. Layer l (W:690-715, M:504-564): h = LN(x); q = (h Wq^T + bq) d^-1/2, k = h Wk^T + bk, v = h Wv^T + bv; for head n,
+ *      u = grep_linear_l(h[t, n d : (n + 1) d]) (8 values), a = sigmoid(u0 + .. + u3), b = sigmoid(u4 + .. + u7),
+ *      gate = a (b grep_a_l[n] - 1) + 2; scores q_t . k_s + gate[b, n, t] bias[n][bucket(s - t)], softmax over s, times v, out_proj,
+ *      + x; then x = x + fc2(gelu(fc1(LN(x)))). grep_linear and grep_a are per layer; relative_attention_bias exists in layer 0 only
+ *      and every layer reuses its table.
+ *   5. Bias buckets (M:417-455), evaluated on the host exactly as the reference does, in torch: n = num_buckets / 2, bucket =
+ *      (rel > 0) n + (|rel| < n / 2 ? |rel| : min(n / 2 + (long)(log(float(|rel|) / (n / 2)) / log(max_distance / (n / 2)) (n - n / 2)),
+ *      n - 1)); the logarithm is float32 and the cast truncates toward zero, so a float64 evaluation can differ at a bucket boundary.
+ *      It becomes the device table bias_rel[H][2 T' - 1], indexed by s - t + T' - 1, cached per T'.
+ *   6. Output: encoder.layer_norm after the last layer -> [B][L'][C]; output_layer = k returns layer k's output without that norm.
+ * Activations are token-major fp32 [B][T][C] at p[b bs + t ts + c]. No atomics, fixed summation orders: bit-identical from call to
+ * call, a row in a batch gets the bits it gets alone; no host synchronisation, graph-capturable.
+ * tdvc_wavlm_gemm: y[b][t][g N + n] = epilogue((sum_k A(b, g, t)[k] w[g N + n][k] + bias[g N + n]) scale_n) [+ res[b][t][g N + n]], n < N,
+ *   g < groups, w [groups N][K]; scale_n = scale for scale_lo <= g N + n < scale_hi, else 1 (the d^-1/2 of q in the fused q|k|v);
+ *   epilogue 0: none, 1: erf-GELU (applied before the residual is added). A(b, g, t) is the K floats at x + b x_bs + g x_gs + t x_ts,
+ *   contiguous (seg_len = 0 or K), or K / seg_len segments of seg_len floats x_ss apart. With x_ts = s Cin and K = k Cin it is a
+ *   strided Conv1d over token-major input (weights permuted to [Cout][k][Cin]). res may be y itself (same strides); y must not
+ *   otherwise overlap x or res. Exact fp32 on v_mfma_f32_16x16x4_f32, 64 tokens x 64 columns per workgroup, chunks of 32 summed from
+ *   zero and then accumulated.
+ * tdvc_wavlm_frames: the frame count after n_layers convolutions, (L - k) / s + 1 each, 0 once a row is shorter than a kernel; -1 on
+ *   bad arguments. Host only.
+ * tdvc_wavlm_conv0: the first convolution (one input channel; w_t [K][C], transposed), its LayerNorm and GELU: x [B] rows of L samples
+ *   -> y [B][(L - K) / stride + 1][C]. Float64 inside, one rounding.
+ * tdvc_wavlm_layernorm: y = LN(x) over rows of C floats (eps 1e-5, biased variance), float64 statistics, one rounding; gelu = 1
+ *   applies erf-GELU. With H > 0 also gate[B][H][T] of item 4 from the normalised (stored) row, grep_w [8][C / H], grep_b [8],
+ *   grep_a [H], float64 inside (a second launch). y may be x.
+ * tdvc_wavlm_posconv: xp [B][T + K - 1][C] (row stride xp_bs) holds the row behind K / 2 zero tokens and in front of K / 2 - 1;
+ *   w [C][K][C / groups] is the folded weight (w = g v / ||v||, evaluated in float64 and rounded once, permuted);
+ *   y[b][t] = xp[b][t + K / 2] + gelu(conv + bias). One launch of the GEMM kernel in its segmented-row mode.
+ * tdvc_wavlm_attention: q, k, v at p[b bs + t ts + n d + c] (q already scaled), gate [B][H][T], bias_rel [H][2 T - 1] ->
+ *   out[b][t][n d + c] = sum_s softmax_s(q_t . k_s + gate[b][n][t] bias_rel[n][s - t + T - 1]) v_s. Keys in tiles of 64 with a
+ *   running maximum and sum; plain fp32.
+ * TDVC_EINVAL: negative sizes or strides, null pointers, strides that are not multiples of 4 floats or operands that are not 16-byte
+ * aligned (gemm, posconv, attention: they move float4), a token stride below the row's width, an unknown epilogue, K not a multiple of
+ * seg_len, a residual that is y with other strides. TDVC_EUNSUPPORTED: N, K, seg_len or C / groups not a multiple of 16, C not a
+ * multiple of 16 or above 1024 (conv0, layernorm), a conv0 kernel above 64 taps or a row shorter than it, an odd positional kernel,
+ * a head width outside {16, 32, 64}, more than 4096 tokens in the attention (82 s), B (x groups) or H > 65535, T > 2^24. All
+ * before any launch; B == 0 is a no-op. */
+typedef struct {
+  int32_t B, T, N, K, groups, seg_len, epilogue, scale_lo, scale_hi;
+  float scale;
+  const float* x; int64_t x_bs, x_ts, x_ss, x_gs;
+  const float* w;                             /* [groups N][K] */
+  const float* bias;                          /* [groups N] or NULL */
+  const float* res; int64_t r_bs, r_ts;       /* NULL: no residual */
+  float* y; int64_t y_bs, y_ts;
+} tdvc_wavlm_gemm_args;
+int tdvc_wavlm_gemm(const tdvc_wavlm_gemm_args* args, void* stream);
+int32_t tdvc_wavlm_frames(int64_t L, int32_t n_layers, const int32_t* kernels, const int32_t* strides);
+int tdvc_wavlm_conv0(const float* x, int64_t x_bs, int32_t B, int32_t L, const float* w_t, int32_t K, int32_t stride, int32_t C,
+                     const float* gamma, const float* beta, float* y, int64_t y_bs, int64_t y_ts, void* stream);
+int tdvc_wavlm_layernorm(const float* x, int64_t x_bs, int64_t x_ts, int32_t B, int32_t T, int32_t C, const float* gamma, const float* beta,
+                         int32_t gelu, float* y, int64_t y_bs, int64_t y_ts, int32_t H, const float* grep_w, const float* grep_b,
+                         const float* grep_a, float* gate, void* stream);
+int tdvc_wavlm_posconv(const float* xp, int64_t xp_bs, int32_t B, int32_t T, int32_t C, int32_t K, int32_t groups, const float* w,
+                       const float* bias, float* y, int64_t y_bs, int64_t y_ts, void* stream);
+int tdvc_wavlm_attention(const float* q, const float* k, const float* v, int64_t bs, int64_t ts, int32_t B, int32_t T, int32_t H, int32_t d,
+                         const float* gate, const float* bias_rel, float* out, int64_t o_bs, int64_t o_ts, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

@@ -13,7 +13,8 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     similarity and nearest-centroid accuracy) as VoiceEncoder / load_voice_encoder / voice_mel / lstm_fwd / partial_slices /
     window_count / speaker_similarity (speaker.py), and the speechbrain speaker recognition of
     test_scripts/mls-pt/test_speaker_rec.py (Fbank features, the ECAPA-TDNN embedding, the cosine classifier) as EcapaTdnn /
-    load_ecapa / fbank / fbank_matrix / speaker_classify / running_mean_norm (ecapa.py).
+    load_ecapa / fbank / fbank_matrix / speaker_classify / running_mean_norm (ecapa.py), and the WavLM feature extractor that
+    model/ssl_encoder.py injects into SSLEncoder (wavlm/WavLM.py extract_features) as WavLM / WavLMConfig / load_wavlm (wavlm.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -28,7 +29,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', 'wavlm', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -44,6 +45,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.speaker'), name)
     if name in ('EcapaTdnn', 'load_ecapa', 'fbank', 'fbank_matrix', 'speaker_classify', 'running_mean_norm'):
         return getattr(importlib.import_module(f'{__name__}.ecapa'), name)
+    if name in ('WavLM', 'WavLMConfig', 'load_wavlm'):
+        return getattr(importlib.import_module(f'{__name__}.wavlm'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

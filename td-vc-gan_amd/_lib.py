@@ -78,6 +78,14 @@ class TdnnArgs(C.Structure):
                 ('y', C.c_void_p), ('y_bs', C.c_int64), ('y_cs', C.c_int64), ('frames', C.c_void_p)]
 
 
+class WavlmGemmArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('T', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('groups', C.c_int32), ('seg_len', C.c_int32),
+                ('epilogue', C.c_int32), ('scale_lo', C.c_int32), ('scale_hi', C.c_int32), ('scale', C.c_float),
+                ('x', C.c_void_p), ('x_bs', C.c_int64), ('x_ts', C.c_int64), ('x_ss', C.c_int64), ('x_gs', C.c_int64),
+                ('w', C.c_void_p), ('bias', C.c_void_p), ('res', C.c_void_p), ('r_bs', C.c_int64), ('r_ts', C.c_int64),
+                ('y', C.c_void_p), ('y_bs', C.c_int64), ('y_ts', C.c_int64)]
+
+
 class L1Pair(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('da', C.c_void_p), ('n', C.c_int64), ('weight', C.c_float)]
 
@@ -95,6 +103,7 @@ POST_NONE, POST_LRELU, POST_TANH = 0, 1, 2
 DG_PLAIN, DG_MASK_LRELU, DG_FILM = 0, 1, 2
 DTW_L2, DTW_L1, DTW_SQ = 0, 1, 2      # tdvc_dtw metric (include/tdvc.h)
 TDNN_NONE, TDNN_RELU_BN, TDNN_RELU_BN_TANH = 0, 1, 2      # tdvc_tdnn_fwd epilogue (include/tdvc.h)
+WAVLM_NONE, WAVLM_GELU = 0, 1      # tdvc_wavlm_gemm epilogue (include/tdvc.h)
 RESAMPLE_TO = 256      # outputs per block of tdvc_resample (= tdvc_resample_tile(), csrc/audio_resample.hip RS_TO)
 
 # name -> (restype, argtypes); every symbol include/tdvc.h declares
@@ -216,6 +225,13 @@ SIGNATURES = {
     'tdvc_asp_pool': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                            C.c_size_t, _vp]),
     'tdvc_ecapa_head': (_i, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    'tdvc_wavlm_gemm': (_i, [C.POINTER(WavlmGemmArgs), _vp]),
+    'tdvc_wavlm_frames': (C.c_int32, [_i64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'tdvc_wavlm_conv0': (_i, [_vp, _i64, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'tdvc_wavlm_layernorm': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _i64, _i64, C.c_int32, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    'tdvc_wavlm_posconv': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'tdvc_wavlm_attention': (_i, [_vp, _vp, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _i64, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

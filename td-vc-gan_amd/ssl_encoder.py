@@ -4,8 +4,8 @@ model/ssl_encoder.py: `WN` (:17-90, gated WaveNet stack), `Encoder` (:93-116, pr
 (`encoder.pre.weight`, `encoder.enc.in_layers.{i}.weight_g/_v/bias`, `encoder.enc.res_skip_layers.{i}...`,
 `encoder.proj.*`).
 
-The frozen WavLM-Large feature extractor itself is OUT of scope of the HIP path (third-party model, stock PyTorch, and
-its checkpoint `wavlm/WavLM-Large.pt` does not ship with the reference): `SSLEncoder` takes it as an injected module
+The frozen WavLM-Large feature extractor is not built here (its checkpoint `wavlm/WavLM-Large.pt` does not ship with the
+reference; `wavlm.WavLM` / `load_wavlm` are that extractor on the HIP path): `SSLEncoder` takes it as an injected module
 `cmodel` (anything with the reference's `extract_features(wave)[0] -> [B, T', 1024]`), runs it under no_grad exactly like
 the reference (:141-145), and keeps it out of the optimizer. Without a `cmodel` the encoder consumes precomputed SSL
 features [B, 1024, T'] directly.
