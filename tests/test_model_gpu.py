@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from common import (GOLDEN, assert_grads_close, assert_update_matches_fixture, build_models, feat_sample_idx, filled_sd, pkg, rel_l2,
-                    to_dev)
+                    to_dev, update_stats)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -217,13 +217,29 @@ def test_graph_replay_matches_eager(dev):
             for _ in range(4):
                 log = ts.run(bt, ix, iy)
         torch.cuda.synchronize()
-        res[mode] = ({k: float(v) for k, v in log.items()}, G.arena.P.detach().clone(), D.arena.P.detach().clone())
+        res[mode] = ({k: float(v) for k, v in log.items()}, G.arena.P.detach().clone(), D.arena.P.detach().clone(),
+                     {f'{t}/{k}': p.detach().cpu().clone() for t, m in (('G', G), ('D', D)) for k, p in m.named_parameters()})
     for k, v in res['eager'][0].items():
         # not bitwise: bias / slab folds use float atomics whose order differs from launch to launch
         assert abs(res['graph'][0][k] - v) <= TOL * (abs(v) + 1e-6), (k, res['graph'][0][k], v)
     # parameters after 4 AdamW steps: early Adam updates are ~lr*sign(g), so last-bit gradient differences (atomics)
     # on near-zero gradient elements move single parameters by 2*lr
     assert rel_l2(res['graph'][1], res['eager'][1]) < 5e-4 and rel_l2(res['graph'][2], res['eager'][2]) < 5e-4
+    # rel_l2 of the parameters cannot see whether an lr = 1e-4 optimizer ran at all (four such steps move p by ~1e-4 relative):
+    # the UPDATE of every tensor since the seeded fill, graph against eager, with the bars of test_loop_switches_gpu._check_updates
+    before = {f'{t}/{k}': v for t in ('G', 'D') for k, v in filled_sd(t).items()}
+    fl, rest, still = [], [], []
+    for k, p_e in res['eager'][3].items():
+        if torch.equal(p_e, before[k]):      # a tensor no loss reaches: untouched in the captured run too
+            assert torch.equal(res['graph'][3][k], before[k]), k
+            still.append(k)
+            continue
+        f, r, dn = update_stats(before[k], res['graph'][3][k], p_e, cfg.lr_g)
+        assert dn > 0 and float((res['graph'][3][k].double() - before[k].double()).norm()) > 0, k
+        fl.append(f); rest.append(r)
+    assert len(fl) > 10 * len(still), (len(fl), still)
+    assert float(np.median(fl)) <= 5e-3 and float(np.max(fl)) <= 0.08, (float(np.median(fl)), float(np.max(fl)))
+    assert float(np.median(rest)) <= 1e-2, float(np.median(rest))
 
 
 def test_f0_to_excitation_device_vs_reference_golden(dev):
