@@ -1,7 +1,9 @@
 """What every operator wrapper (pitch, corrupt, resample, evaluate, util) does on the host before its launch, defined once: the
-device check, strided [B, T] / [B, N, D] views with the strides the C ABI takes, scratch, optional pointers, the current stream,
-host tables uploaded once per device, and TDVC_EUNSUPPORTED as ValueError. Nothing here synchronises with the host. Torch tensors
+device check, strided [B, T] / [B, N, D] views with the strides the C ABI takes, per-row lengths and parameter vectors as the kernels
+read them, scratch, optional pointers, the current stream, host tables uploaded once per device (the DFT table prefix of the two mel
+front ends among them), and TDVC_EUNSUPPORTED as ValueError. Nothing here synchronises with the host. Torch tensors
 have no negative strides (as_strided refuses them, flip copies), so the layout helpers do not look for them."""
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -69,6 +71,38 @@ def frames3(who, t):
     if (D > 1 and t3.stride(2) != 1) or (N > 1 and t3.stride(1) < D):
         t3 = t3.contiguous()
     return t3, (t3.stride(0) if t3.shape[0] > 1 else N * D), (t3.stride(1) if N > 1 else D)
+
+
+def device_lengths(who, lengths, B, device, move=False, any_shape=False):
+    """lengths (None, a sequence or a tensor) -> None or int32 contiguous [B] on `device`. A sequence is uploaded; a tensor must be
+    on a device already (TdvcError) unless `move` takes it there. The shape must be (B,) unless `any_shape` takes any B elements."""
+    if lengths is None:
+        return None
+    if not torch.is_tensor(lengths):
+        lengths = torch.as_tensor(lengths, device=device)
+    elif move:
+        lengths = lengths.to(device)
+    else:
+        need_device(who, lengths)
+    if lengths.numel() != B if any_shape else lengths.shape != (B,):
+        raise ValueError(f'{who}: lengths must be [{B}]' + (' or any shape of that many elements' if any_shape else ''))
+    return lengths.reshape(-1).to(torch.int32).contiguous()
+
+
+def vec(who, t, n, name='a vector'):
+    """A parameter of n elements in any shape -> flat fp32 contiguous device tensor [n], detached."""
+    need_device(who, t)
+    if t.numel() != n:
+        raise ValueError(f'{who}: {name} has {t.numel()} elements, expected {n}')
+    return t.detach().float().contiguous().reshape(-1)
+
+
+def dft_tables(n_fft, window):
+    """float64 [cos | sin | window] of 2 pi i / n_fft, n_fft values each: the table of csrc/dft400.h up to the caller's filterbank.
+    window: (a, b) for a - b cos (Hann 0.5, 0.5; Hamming 0.54, 0.46), or the n_fft values themselves."""
+    ang = 2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft
+    window = window[0] - window[1] * np.cos(ang) if len(window) == 2 else np.asarray(window, dtype=np.float64).reshape(n_fft)
+    return np.concatenate([np.cos(ang), np.sin(ang), window])
 
 
 def host_table(key, build):

@@ -11,7 +11,7 @@
 //     P, R [h + 1]    power spectrum, later the liftered cepstrum c; log of the smoothed spectrum
 // 53 KB at N = 2048, 27 KB at 1024: 3 and 5 blocks per CU.
 //   window     thread t owns samples t, t + 256, ... of the (at most N - 3) window samples in registers; sum w^2, sum x w, sum w:
-//              per-thread partials in ascending order, a shuffle butterfly per wave, the 4 wave sums added in order
+//              per-thread partials in ascending order, a shuffle butterfly per wave, the 4 wave sums added pairwise (reduce.h)
 //   transform  a real sequence of N points is packed as h complex points z[j] = v[2j] + i v[2j+1] in bit-reversed order, h/2
 //              in-place radix-2 butterflies per stage (log2 h stages, one barrier each), then the split X[k] = E[k] + w^k O[k].
 //              The lanes of a wave touch 32 values out of 64 consecutive ones (stages m < 32: 2-way on the 64-bit banks) or 32
@@ -29,6 +29,7 @@
 #include "../../include/tdvc.h"
 #include "api_util.h"
 #include "conv_common.h"
+#include "reduce.h"
 
 namespace tdvc {
 
@@ -54,12 +55,6 @@ struct CtLds {
   double P[H + 1], R[H + 1];
   double red[3][CT_THREADS / 64];
 };
-
-__device__ __forceinline__ double ct_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // v(n), n < N, real -> packed complex in bit-reversed order
 template <int N, typename Fn>
@@ -138,7 +133,7 @@ __global__ __launch_bounds__(CT_THREADS) void cheaptrick_kernel(CtP p) {
   if (!isfinite(f0v) || !(fe > 3.0 * fs / (N - 3.0) && fe <= fs / 4.0)) fe = CT_DEFAULT_F0;
   const int half = min((int)floor(1.5 * fs / fe + 0.5), (N - 4) / 2);
   const int wlen = 2 * half + 1;
-  const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+  const int len = row_len(p.lengths, b, p.T);
   const long pos = f * (long)p.hop;
   const float* xrow = p.x + b * p.x_bs;
 
@@ -155,12 +150,10 @@ __global__ __launch_bounds__(CT_THREADS) void cheaptrick_kernel(CtP p) {
       sw2 = fma(w[e], w[e], sw2); sxw = fma(xv[e], w[e], sxw); sw += w[e];
     }
   }
-  sw2 = ct_wave_sum(sw2); sxw = ct_wave_sum(sxw); sw = ct_wave_sum(sw);
+  sw2 = wave_sum(sw2); sxw = wave_sum(sxw); sw = wave_sum(sw);
   if (lane == 0) { s.red[0][wv] = sw2; s.red[1][wv] = sxw; s.red[2][wv] = sw; }
   __syncthreads();
-  sw2 = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
-  sxw = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
-  sw = (s.red[2][0] + s.red[2][1]) + (s.red[2][2] + s.red[2][3]);
+  sw2 = sum_pairwise(s.red[0]); sxw = sum_pairwise(s.red[1]); sw = sum_pairwise(s.red[2]);
   const double nrm = sqrt(sw2), mean = sxw / sw;
   {
     constexpr int LOG = __builtin_ctz(H);
@@ -244,7 +237,7 @@ __global__ __launch_bounds__(CT_THREADS) void cheaptrick_kernel(CtP p) {
       const double* row = p.G + (long)o * (H + 1);
       double acc = 0.0;
       for (int k = lane; k <= H; k += 64) acc = fma(row[k], k == 0 ? 0.5 * s.P[0] : s.P[k], acc);
-      acc = ct_wave_sum(acc);
+      acc = wave_sum(acc);
       if (lane == 0) out[o] = (float)acc;
     }
   }

@@ -42,10 +42,9 @@ struct DtwP {
   unsigned* dirs; long dirs_bs; int dirs_rs;               // [B][N][ceil(M / 16)] directions, NULL without a path
 };
 
-static inline size_t dtw_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int dtw_dir_words(int M) { return (M + 15) / 16; }
-static inline size_t dtw_bnd_c_bytes(int B, int M) { return dtw_align((size_t)B * M * sizeof(double)); }
-static inline size_t dtw_bnd_l_bytes(int B, int M) { return dtw_align((size_t)B * M * sizeof(int)); }
+static inline size_t dtw_bnd_c_bytes(int B, int M) { return tdvc_align256((size_t)B * M * sizeof(double)); }
+static inline size_t dtw_bnd_l_bytes(int B, int M) { return tdvc_align256((size_t)B * M * sizeof(int)); }
 static constexpr size_t dtw_lds_bytes(int DT, int BH) { return DTW_FIXED_LDS + (size_t)(BH + DTW_CH) * (DT | 1) * sizeof(float); }
 
 template <int DT, int BH>

@@ -3,7 +3,7 @@
 // padded batch is evaluated as if it were alone.
 //
 // tdvc_fbank       pass 1, one block per 8 frames of a row: Hamming window, a direct 400-point float64 DFT against a cos/sin table
-//                  in LDS, power, the mel sums, 10 log10(max(., 1e-10)) into the workspace and the block's maximum; pass 2, one
+//                  in LDS, power (dft400.h), the mel sums, 10 log10(max(., 1e-10)) into the workspace and the block's maximum; pass 2, one
 //                  block per (band, row): the row maximum folded from the block maxima, the M - 80 floor, the mean over the row's
 //                  frames in a fixed order, one rounding at the store; writes the row's frame count
 // tdvc_tdnn_fwd    the reflect-padded, length-aware Conv1d as an implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32), below
@@ -33,26 +33,16 @@
 #include "../../include/tdvc.h"
 #include "api_util.h"
 #include "conv_common.h"
+#include "dft400.h"
+#include "reduce.h"
 
 namespace tdvc {
 
-constexpr int FB_NFFT = 400, FB_HOP = 160, FB_BINS = 201, FB_FR = 8, FB_MAXMEL = 128;
+constexpr int FB_MAXMEL = 128;
 constexpr int TD_TN = 64, TD_TM = 64, TD_XW = 80, TD_THREADS = 256;
 constexpr int SE_MAXC = 65532;      // grid.y of the apply launch
 
 typedef float ec_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double ec_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ double ec_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ int ec_frames(const int* frames, int b, int F) { return frames ? min(max(frames[b], 0), F) : F; }
 
 // ------------------------------------------------------------------------------------------------------------------ Fbank
 struct FbankP {
@@ -66,79 +56,59 @@ struct FbankP {
 };
 
 __global__ __launch_bounds__(256) void fbank_db_kernel(FbankP p) {
-  __shared__ double cs[2 * FB_NFFT];
-  __shared__ double xw[FB_FR][FB_NFFT];
-  __shared__ double pw[FB_FR][FB_BINS];
+  __shared__ double cs[2 * DFT_NFFT];
+  __shared__ double xw[DFT_FR][DFT_NFFT];
+  __shared__ double pw[DFT_FR][DFT_BINS];
   __shared__ double red[4];
   const int t = threadIdx.x, b = blockIdx.y;
-  const int f0 = blockIdx.x * FB_FR;
-  const int n = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
-  const int nfr = 1 + n / FB_HOP;
+  const int f0 = blockIdx.x * DFT_FR;
+  const int n = row_len(p.lengths, b, p.T);
+  const int nfr = 1 + n / DFT_HOP;
   if (f0 >= nfr) {                                                          // uniform: nothing of this row is read here
     if (t == 0) p.bmax[(long)b * p.nblk + blockIdx.x] = -INFINITY;
     return;
   }
   const float* row = p.x + b * p.x_bs;
-  for (int i = t; i < 2 * FB_NFFT; i += 256) cs[i] = p.tab[i];
-  for (int idx = t; idx < FB_FR * FB_NFFT; idx += 256) {
-    const int fr = idx / FB_NFFT, i = idx - fr * FB_NFFT;
-    const long q = (long)(f0 + fr) * FB_HOP - FB_NFFT / 2 + i;
+  for (int i = t; i < 2 * DFT_NFFT; i += 256) cs[i] = p.tab[i];
+  for (int idx = t; idx < DFT_FR * DFT_NFFT; idx += 256) {
+    const int fr = idx / DFT_NFFT, i = idx - fr * DFT_NFFT;
+    const long q = (long)(f0 + fr) * DFT_HOP - DFT_NFFT / 2 + i;
     double v = 0.0;
-    if (f0 + fr < nfr && q >= 0 && q < n) v = (double)row[q] * p.tab[2 * FB_NFFT + i];
+    if (f0 + fr < nfr && q >= 0 && q < n) v = (double)row[q] * p.tab[DFT_TAB_WINDOW + i];
     xw[fr][i] = v;
   }
   __syncthreads();
-  for (int item = t; item < FB_FR * FB_BINS; item += 256) {
-    const int fr = item / FB_BINS, k = item - fr * FB_BINS;
-    double re = 0.0, im = 0.0;
-    int m = 0;
-    for (int i = 0; i < FB_NFFT; ++i) {
-      const double v = xw[fr][i];
-      re = fma(v, cs[m], re);
-      im = fma(v, cs[FB_NFFT + m], im);
-      m += k;
-      if (m >= FB_NFFT) m -= FB_NFFT;
-    }
-    pw[fr][k] = re * re + im * im;
-  }
+  dft400_power<256>(cs, xw, pw, t);
   __syncthreads();
-  const double* fb = p.tab + 3 * FB_NFFT;
+  const double* fb = p.tab + DFT_TAB_FB;
   double mx = -INFINITY;
-  for (int item = t; item < FB_FR * p.M; item += 256) {
-    const int m = item / FB_FR, fr = item - m * FB_FR;
+  for (int item = t; item < DFT_FR * p.M; item += 256) {
+    const int m = item / DFT_FR, fr = item - m * DFT_FR;
     const int f = f0 + fr;
     if (f >= nfr) continue;
     double acc = 0.0;
-    for (int k = 0; k < FB_BINS; ++k) acc = fma(fb[m * FB_BINS + k], pw[fr][k], acc);
+    for (int k = 0; k < DFT_BINS; ++k) acc = fma(fb[m * DFT_BINS + k], pw[fr][k], acc);
     const double d = 10.0 * log10(fmax(acc, 1e-10));
     p.db[((long)b * p.M + m) * p.F + f] = d;
     mx = fmax(mx, d);
   }
-  mx = ec_wave_max(mx);
-  if ((t & 63) == 0) red[t >> 6] = mx;
-  __syncthreads();
-  if (t == 0) p.bmax[(long)b * p.nblk + blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  mx = block_max<4>(mx, red, t);
+  if (t == 0) p.bmax[(long)b * p.nblk + blockIdx.x] = mx;
 }
 
 __global__ __launch_bounds__(256) void fbank_norm_kernel(FbankP p) {
   __shared__ double red[4];
   const int t = threadIdx.x, m = blockIdx.x, b = blockIdx.y;
-  const int n = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
-  const int nfr = 1 + n / FB_HOP, nb = (nfr + FB_FR - 1) / FB_FR;
+  const int n = row_len(p.lengths, b, p.T);
+  const int nfr = 1 + n / DFT_HOP, nb = (nfr + DFT_FR - 1) / DFT_FR;
   double mx = -INFINITY;
   for (int i = t; i < nb; i += 256) mx = fmax(mx, p.bmax[(long)b * p.nblk + i]);
-  mx = ec_wave_max(mx);
-  if ((t & 63) == 0) red[t >> 6] = mx;
-  __syncthreads();
-  const double floor_db = fmax(fmax(red[0], red[1]), fmax(red[2], red[3])) - 80.0;
-  __syncthreads();
+  const double floor_db = block_max<4>(mx, red, t) - 80.0;
+  __syncthreads();                                                          // red is written again below
   const double* d = p.db + ((long)b * p.M + m) * p.F;
   double s = 0.0;
   for (int f = t; f < nfr; f += 256) s += fmax(d[f], floor_db);
-  s = ec_wave_sum(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  const double mean = ((red[0] + red[1]) + (red[2] + red[3])) / (double)nfr;
+  const double mean = block_sum_pairwise(s, red, t) / (double)nfr;
   float* o = p.out + b * p.o_bs + m * p.o_cs;
   for (int f = t; f < p.F; f += 256) o[f] = f < nfr ? (float)(fmax(d[f], floor_db) - mean) : 0.f;
   if (m == 0 && t == 0) p.frames[b] = nfr;
@@ -162,7 +132,7 @@ __global__ __launch_bounds__(TD_THREADS, 2) void tdnn_fwd_kernel(TdnnP p) {
   __shared__ float ws[TD_TM * WA];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, j = lane & 15, q = lane >> 4;
   const int b = blockIdx.z, t0 = blockIdx.x * TD_TN, co_blk = blockIdx.y * TD_TM;
-  const int n = ec_frames(p.frames, b, p.F);
+  const int n = row_len(p.frames, b, p.F);
   if (t0 >= n) return;                                                      // uniform: frames at and past n are not written
   const int pad = (K - 1) * p.dil / 2, span = TD_TN + 2 * pad;              // pad <= 4: span <= 72 < TD_XW
   const int tend = min(t0 + TD_TN, n);
@@ -302,11 +272,11 @@ static void tdnn_launch(const tdvc_tdnn_args* a, hipStream_t st) {
 // gate is [B][C + S]: the means, then the gates, in the first C floats of a row, the hidden layer in the last S
 __global__ __launch_bounds__(256) void se_mean_kernel(const float* x, long x_bs, long x_cs, int C, int S, int F, const int* frames, float* gate) {
   const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-  const int n = ec_frames(frames, b, F);
+  const int n = row_len(frames, b, F);
   const float* r = x + b * x_bs + c * x_cs;
   double s = 0.0;
   for (int f = lane; f < n; f += 64) s += (double)r[f];
-  s = ec_wave_sum(s);
+  s = wave_sum(s);
   if (lane == 0) gate[(long)b * (C + S) + c] = n > 0 ? (float)(s / (double)n) : 0.f;
 }
 
@@ -317,14 +287,14 @@ __global__ __launch_bounds__(256) void se_fc_kernel(float* gate, int stride, int
   const float* wr = w + (long)o * N;
   double acc = 0.0;
   for (int i = lane; i < N; i += 64) acc = fma((double)wr[i], (double)in[i], acc);
-  acc = ec_wave_sum(acc) + (double)bias[o];
+  acc = wave_sum(acc) + (double)bias[o];
   if (lane == 0) gate[(long)b * stride + out_off + o] = act ? (float)(1.0 / (1.0 + exp(-acc))) : fmaxf((float)acc, 0.f);
 }
 
 __global__ __launch_bounds__(256) void se_apply_kernel(const float* x, long x_bs, long x_cs, const float* res, long r_bs, long r_cs, const float* gate,
                                                        int C, int S, int F, const int* frames, float* y, long y_bs, long y_cs) {
   const int f = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
-  if (f >= ec_frames(frames, b, F)) return;
+  if (f >= row_len(frames, b, F)) return;
   const float g = gate[(long)b * (C + S) + c];
   y[b * y_bs + c * y_cs + f] = fmaf(g, x[b * x_bs + c * x_cs + f], res[b * r_bs + c * r_cs + f]);
 }
@@ -334,7 +304,7 @@ __global__ __launch_bounds__(256) void se_apply_kernel(const float* x, long x_bs
 __global__ __launch_bounds__(256) void asp_stats_kernel(const float* x, long x_bs, long x_cs, const float* lg, int C, int F, const int* frames,
                                                         float* out) {
   const int lane = threadIdx.x & 63, c = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-  const int n = ec_frames(frames, b, F);
+  const int n = row_len(frames, b, F);
   float* o = out + (long)b * 2 * C;
   if (n == 0) { if (lane == 0) { o[c] = 0.f; o[C + c] = 0.f; } return; }
   const float* r = x + b * x_bs + c * x_cs;
@@ -342,20 +312,20 @@ __global__ __launch_bounds__(256) void asp_stats_kernel(const float* x, long x_b
   double mx = -INFINITY, den = (double)n;
   if (l) {
     for (int f = lane; f < n; f += 64) mx = fmax(mx, (double)l[f]);
-    mx = ec_wave_max(mx);
+    mx = wave_max(mx);
     den = 0.0;
     for (int f = lane; f < n; f += 64) den += exp((double)l[f] - mx);
-    den = ec_wave_sum(den);
+    den = wave_sum(den);
   }
   double m = 0.0;
   for (int f = lane; f < n; f += 64) m = fma(l ? exp((double)l[f] - mx) : 1.0, (double)r[f], m);
-  m = ec_wave_sum(m) / den;
+  m = wave_sum(m) / den;
   double v = 0.0;
   for (int f = lane; f < n; f += 64) {
     const double d = (double)r[f] - m;
     v = fma(l ? exp((double)l[f] - mx) : 1.0, d * d, v);
   }
-  v = ec_wave_sum(v) / den;
+  v = wave_sum(v) / den;
   if (lane == 0) { o[c] = (float)m; o[C + c] = (float)sqrt(fmax(v, 1e-12)); }
 }
 
@@ -366,7 +336,7 @@ __global__ __launch_bounds__(256) void asp_rowbias_kernel(const float* w, const 
   const float* m = ms + (long)b * 2 * C;
   double acc = 0.0;
   for (int jx = lane; jx < 2 * C; jx += 64) acc = fma((double)wr[jx], (double)m[jx], acc);
-  acc = ec_wave_sum(acc);
+  acc = wave_sum(acc);
   if (lane == 0) rb[(long)b * A + a] = (float)acc;
 }
 
@@ -377,21 +347,19 @@ __global__ __launch_bounds__(256) void ecapa_head_kernel(const float* pooled, co
   const float* wr = w + (long)e * N;
   double acc = 0.0;
   for (int jx = lane; jx < N; jx += 64) acc = fma((double)wr[jx], (double)fmaf(pr[jx], scale[jx], shift[jx]), acc);
-  acc = ec_wave_sum(acc);
+  acc = wave_sum(acc);
   if (lane == 0) out[(long)b * E + e] = (float)(acc + (double)bias[e]);
 }
-
-static inline size_t ec_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct AspPlan { size_t ms, rb, h, lg, total; };
 static bool asp_plan(int B, int C, int A, int F, AspPlan* pl) {
   if (B < 1 || C < 16 || A < 16 || F < 5 || C % 16 || A % 16 || B > 65535 || C > (1 << 20) || A > (1 << 20) || F > (1 << 24)) return false;
   if ((double)B * C * F > (double)(1L << 36)) return false;
   size_t off = 0;
-  pl->ms = off; off += ec_align((size_t)B * 2 * C * 4);
-  pl->rb = off; off += ec_align((size_t)B * A * 4);
-  pl->h = off; off += ec_align((size_t)B * A * F * 4);
-  pl->lg = off; off += ec_align((size_t)B * C * F * 4);
+  pl->ms = off; off += tdvc_align256((size_t)B * 2 * C * 4);
+  pl->rb = off; off += tdvc_align256((size_t)B * A * 4);
+  pl->h = off; off += tdvc_align256((size_t)B * A * F * 4);
+  pl->lg = off; off += tdvc_align256((size_t)B * C * F * 4);
   pl->total = off;
   return true;
 }
@@ -403,8 +371,8 @@ static bool fbank_ok(int B, int T, int M) { return B >= 1 && B <= 65535 && T >= 
 extern "C" size_t tdvc_fbank_workspace(int32_t B, int32_t T, int32_t n_mels) {
   using namespace tdvc;
   if (!fbank_ok(B, T, n_mels)) return 0;
-  const size_t F = 1 + T / FB_HOP, nblk = (F + FB_FR - 1) / FB_FR;
-  return ec_align((size_t)B * n_mels * F * 8) + ec_align((size_t)B * nblk * 8);
+  const size_t F = 1 + T / DFT_HOP, nblk = (F + DFT_FR - 1) / DFT_FR;
+  return tdvc_align256((size_t)B * n_mels * F * 8) + tdvc_align256((size_t)B * nblk * 8);
 }
 
 extern "C" int tdvc_fbank(const float* signal, int64_t s_bs, const int32_t* lengths, int32_t T, int32_t B, int32_t n_mels, const double* tables,
@@ -415,15 +383,15 @@ extern "C" int tdvc_fbank(const float* signal, int64_t s_bs, const int32_t* leng
   if (n_mels < 16 || n_mels > FB_MAXMEL || n_mels % 16) return tdvc_fail(TDVC_EUNSUPPORTED, "fbank: n_mels must be a multiple of 16 up to 128");
   if (T < 640) return tdvc_fail(TDVC_EUNSUPPORTED, "fbank: rows of fewer than 640 samples (5 frames)");
   if (T > (1 << 26) || B > 65535) return tdvc_fail(TDVC_EUNSUPPORTED, "fbank: T > 2^26 or B > 65535");
-  if (F != 1 + T / FB_HOP) return tdvc_fail(TDVC_EINVAL, "fbank: F must be 1 + T / 160");
+  if (F != 1 + T / DFT_HOP) return tdvc_fail(TDVC_EINVAL, "fbank: F must be 1 + T / 160");
   if (f_cs < F) return tdvc_fail(TDVC_EINVAL, "fbank: band stride below F");
   if (B == 0) return TDVC_OK;
   if (!signal || !tables || !feats || !frames) return tdvc_fail(TDVC_EINVAL, "fbank: null pointer");
   const size_t need = tdvc_fbank_workspace(B, T, n_mels);
   if (!workspace || workspace_bytes < need) return tdvc_fail(TDVC_EWORKSPACE, "fbank: workspace too small (tdvc_fbank_workspace)");
   FbankP p;
-  p.x = signal; p.x_bs = s_bs; p.lengths = lengths; p.T = T; p.F = F; p.M = n_mels; p.nblk = (F + FB_FR - 1) / FB_FR; p.tab = tables;
-  p.db = (double*)workspace; p.bmax = (double*)((char*)workspace + ec_align((size_t)B * n_mels * F * 8));
+  p.x = signal; p.x_bs = s_bs; p.lengths = lengths; p.T = T; p.F = F; p.M = n_mels; p.nblk = (F + DFT_FR - 1) / DFT_FR; p.tab = tables;
+  p.db = (double*)workspace; p.bmax = (double*)((char*)workspace + tdvc_align256((size_t)B * n_mels * F * 8));
   p.out = feats; p.o_bs = f_bs; p.o_cs = f_cs; p.frames = frames;
   hipLaunchKernelGGL(fbank_db_kernel, dim3(p.nblk, B), dim3(256), 0, (hipStream_t)stream, p);
   hipLaunchKernelGGL(fbank_norm_kernel, dim3(n_mels, B), dim3(256), 0, (hipStream_t)stream, p);

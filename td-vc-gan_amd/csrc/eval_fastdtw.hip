@@ -58,7 +58,6 @@ struct FdtwP {
   ulonglong2* dirs;                                         // [B][N + M]: direction bit 0 / bit 1 of the 64 lanes of every anti-diagonal
 };
 
-static inline size_t fd_align(size_t v) { return (v + 255) & ~(size_t)255; }
 // Workspace of one call, an upper bound by construction:
 //   pyramids    sum_{l >= 1} floor(n / 2^l) <= n - 1 < N frames of D floats per side
 //   window      lo, hi and the path's first / last column: one int32 per row of a level, n_l <= N
@@ -70,14 +69,14 @@ struct FdtwWs { size_t xpyr, ypyr, lo, hi, jmin, jmax, ifirst, dirs, total; };
 static inline FdtwWs fd_workspace(int B, int N, int M, int D) {
   FdtwWs w;
   size_t o = 0;
-  w.xpyr = o; o += fd_align((size_t)B * N * D * sizeof(float));
-  w.ypyr = o; o += fd_align((size_t)B * M * D * sizeof(float));
-  w.lo = o; o += fd_align((size_t)B * N * sizeof(int));
-  w.hi = o; o += fd_align((size_t)B * N * sizeof(int));
-  w.jmin = o; o += fd_align((size_t)B * N * sizeof(int));
-  w.jmax = o; o += fd_align((size_t)B * N * sizeof(int));
-  w.ifirst = o; o += fd_align((size_t)B * ((size_t)N + M) * sizeof(int));
-  w.dirs = o; o += fd_align((size_t)B * ((size_t)N + M) * sizeof(ulonglong2));
+  w.xpyr = o; o += tdvc_align256((size_t)B * N * D * sizeof(float));
+  w.ypyr = o; o += tdvc_align256((size_t)B * M * D * sizeof(float));
+  w.lo = o; o += tdvc_align256((size_t)B * N * sizeof(int));
+  w.hi = o; o += tdvc_align256((size_t)B * N * sizeof(int));
+  w.jmin = o; o += tdvc_align256((size_t)B * N * sizeof(int));
+  w.jmax = o; o += tdvc_align256((size_t)B * N * sizeof(int));
+  w.ifirst = o; o += tdvc_align256((size_t)B * ((size_t)N + M) * sizeof(int));
+  w.dirs = o; o += tdvc_align256((size_t)B * ((size_t)N + M) * sizeof(ulonglong2));
   w.total = o;
   return w;
 }

@@ -5,8 +5,8 @@
 // tdvc_voice_windows   one thread per row: window count, (row, start frame) per slot, from the device lengths
 // tdvc_voice_gain      one block per row: sum of squares in float64, fixed order -> the volume gain of normalize=True
 // tdvc_voice_mel       one block per 8 frames of a row: the padded-row index mapping, Hann window, a direct 400-point float64 DFT
-//                      against a cos/sin table of 400 entries held in LDS (index k i mod 400), power, the 40 mel sums in float64,
-//                      one rounding at the store
+//                      against a cos/sin table of 400 entries held in LDS (index k i mod 400), power (that stage: dft400.h), the 40
+//                      mel sums in float64, one rounding at the store
 // tdvc_lstm_fwd        per layer: pack W_ih / W_hh into the MFMA operand order (lstm_pack_kernel), the input projection of every
 //                      frame as one GEMM (lstm_proj_kernel), then the recurrence (lstm_rec_kernel)
 // tdvc_voice_embed     one block per row: linear + ReLU + L2 norm per window, the mean over the row's windows, the second norm
@@ -28,50 +28,40 @@
 // section 3).
 // The input projection x_t W_ih^T + b_ih + b_hh is hoisted out of the time loop; layer 0 projects every frame of an
 // utterance once, not once per overlapping window. Its result initialises the accumulators of the step.
-// No atomics anywhere; every sum has a fixed order: bit-identical from call to call.
+// No atomics anywhere; every sum has a fixed order (block sums: the pairwise order of reduce.h): bit-identical from call to call.
 #include <math.h>
 
 #include "../../include/tdvc.h"
 #include "api_util.h"
 #include "conv_common.h"
+#include "dft400.h"
+#include "reduce.h"
 
 namespace tdvc {
 
-constexpr int VM_NFFT = 400, VM_HOP = 160, VM_BINS = 201, VM_MELS = 40, VM_WIN = 160;   // window of 160 frames = 25600 samples
-constexpr int VM_FR = 8;                                                                // frames per block of the mel kernel
+constexpr int VM_MELS = 40, VM_WIN = 160;                                               // window of 160 frames = 25600 samples
 constexpr int LS_H = 256, LS_G = 4 * LS_H, LS_M = 16, LS_LDA = LS_H + 4, LS_THREADS = 512;
 
 // compute_partial_slices in closed form: the number of kept windows of a row of n samples and its padded length L'.
 __host__ __device__ inline int vw_count(long n, int frame_step, double min_cov, long* padded) {
-  const long n_frames = (n + 1 + VM_HOP - 1) / VM_HOP;
+  const long n_frames = (n + 1 + DFT_HOP - 1) / DFT_HOP;
   long steps = n_frames - VM_WIN + frame_step + 1;
   if (steps < 1) steps = 1;
   long cnt = (steps + frame_step - 1) / frame_step;
   if (cnt > 1) {
-    const long first = (long)VM_HOP * (cnt - 1) * frame_step;
-    if ((double)(n - first) / (double)(VM_HOP * VM_WIN) < min_cov) --cnt;
+    const long first = (long)DFT_HOP * (cnt - 1) * frame_step;
+    if ((double)(n - first) / (double)(DFT_HOP * VM_WIN) < min_cov) --cnt;
   }
-  const long end = (long)VM_HOP * ((cnt - 1) * frame_step + VM_WIN);
+  const long end = (long)DFT_HOP * ((cnt - 1) * frame_step + VM_WIN);
   if (padded) *padded = n > end ? n : end;
   return (int)cnt;
-}
-
-__device__ __forceinline__ double vs_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ float vs_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void voice_windows_kernel(const int* lengths, int T, int B, int frame_step, double min_cov, int P_max,
                                                             int* counts, int* slots) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
-  const int n = lengths ? min(max(lengths[b], 0), T) : T;
+  const int n = row_len(lengths, b, T);
   const int cnt = min(vw_count(n, frame_step, min_cov, nullptr), P_max);
   counts[b] = cnt;
   for (int j = 0; j < P_max; ++j) {
@@ -83,15 +73,13 @@ __global__ __launch_bounds__(256) void voice_windows_kernel(const int* lengths, 
 __global__ __launch_bounds__(256) void voice_gain_kernel(const float* x, long x_bs, const int* lengths, int T, double* gain) {
   __shared__ double red[4];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int n = lengths ? min(max(lengths[b], 0), T) : T;
+  const int n = row_len(lengths, b, T);
   const float* row = x + b * x_bs;
   double acc = 0.0;
   for (int i = t; i < n; i += 256) { const double v = (double)row[i]; acc = fma(v, v, acc); }
-  acc = vs_wave_sum(acc);
-  if ((t & 63) == 0) red[t >> 6] = acc;
-  __syncthreads();
+  block_stage(wave_sum(acc), red, t);
   if (t == 0) {
-    const double ss = (red[0] + red[1]) + (red[2] + red[3]);
+    const double ss = (red[0] + red[1]) + (red[2] + red[3]);     // sum_pairwise, spelled out: as a call the branch below compiles differently
     double g = 1.0;
     if (n > 0 && ss > 0.0) {
       const double rms = sqrt(ss / (double)n);
@@ -111,55 +99,43 @@ struct MelP {
 };
 
 __global__ __launch_bounds__(256) void voice_mel_kernel(MelP p) {
-  __shared__ double cs[2 * VM_NFFT];
-  __shared__ double xw[VM_FR][VM_NFFT];
-  __shared__ double pw[VM_FR][VM_BINS];
+  __shared__ double cs[2 * DFT_NFFT];
+  __shared__ double xw[DFT_FR][DFT_NFFT];
+  __shared__ double pw[DFT_FR][DFT_BINS];
   const int t = threadIdx.x, b = blockIdx.y;
-  const int f0 = blockIdx.x * VM_FR;
-  const int n = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+  const int f0 = blockIdx.x * DFT_FR;
+  const int n = row_len(p.lengths, b, p.T);
   long Lp;
   vw_count(n, p.frame_step, p.min_cov, &Lp);
-  const long nfr = 1 + Lp / VM_HOP;
+  const long nfr = 1 + Lp / DFT_HOP;
   const double g = p.gain ? p.gain[b] : 1.0;
   const float* row = p.x + b * p.x_bs;
-  for (int i = t; i < 2 * VM_NFFT; i += 256) cs[i] = p.tab[i];
-  for (int idx = t; idx < VM_FR * VM_NFFT; idx += 256) {
-    const int fr = idx / VM_NFFT, i = idx - fr * VM_NFFT;
+  for (int i = t; i < 2 * DFT_NFFT; i += 256) cs[i] = p.tab[i];
+  for (int idx = t; idx < DFT_FR * DFT_NFFT; idx += 256) {
+    const int fr = idx / DFT_NFFT, i = idx - fr * DFT_NFFT;
     const long f = f0 + fr;
     double v = 0.0;
     if (f < nfr) {
-      long q = f * VM_HOP - VM_NFFT / 2 + i;
+      long q = f * DFT_HOP - DFT_NFFT / 2 + i;
       if (!p.pad_const) {                                                   // L' >= 25600: one reflection reaches every index
         if (q < 0) q = -q;
         if (q >= Lp) q = 2 * (Lp - 1) - q;
       }
-      if (q >= 0 && q < n) v = (double)row[q] * g * p.tab[2 * VM_NFFT + i];
+      if (q >= 0 && q < n) v = (double)row[q] * g * p.tab[DFT_TAB_WINDOW + i];
     }
     xw[fr][i] = v;
   }
   __syncthreads();
-  for (int item = t; item < VM_FR * VM_BINS; item += 256) {
-    const int fr = item / VM_BINS, k = item - fr * VM_BINS;
-    double re = 0.0, im = 0.0;
-    int m = 0;
-    for (int i = 0; i < VM_NFFT; ++i) {
-      const double v = xw[fr][i];
-      re = fma(v, cs[m], re);
-      im = fma(v, cs[VM_NFFT + m], im);
-      m += k;
-      if (m >= VM_NFFT) m -= VM_NFFT;
-    }
-    pw[fr][k] = re * re + im * im;
-  }
+  dft400_power<256>(cs, xw, pw, t);
   __syncthreads();
-  const double* fb = p.tab + 3 * VM_NFFT;
-  for (int item = t; item < VM_FR * VM_MELS; item += 256) {
+  const double* fb = p.tab + DFT_TAB_FB;
+  for (int item = t; item < DFT_FR * VM_MELS; item += 256) {
     const int fr = item / VM_MELS, m = item - fr * VM_MELS;
     const long f = f0 + fr;
     if (f >= p.F) continue;
     double acc = 0.0;
     if (f < nfr)
-      for (int k = 0; k < VM_BINS; ++k) acc = fma(fb[m * VM_BINS + k], pw[fr][k], acc);
+      for (int k = 0; k < DFT_BINS; ++k) acc = fma(fb[m * DFT_BINS + k], pw[fr][k], acc);
     p.out[((long)b * p.F + f) * VM_MELS + m] = (float)acc;
   }
 }
@@ -350,16 +326,6 @@ struct EmbP {
   float* partial; float* utt;
 };
 
-// sum of v over the block's 256 threads in a fixed order; leaves a barrier behind so that red can be reused
-__device__ __forceinline__ float emb_block_sum(float v, float* red, int t) {
-  v = vs_wave_sum(v);
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  const float r = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(256) void voice_embed_kernel(EmbP p) {
   __shared__ float hs[LS_H], e[LS_H], red[4];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.x;
@@ -378,24 +344,25 @@ __global__ __launch_bounds__(256) void voice_embed_kernel(EmbP p) {
       float acc = 0.f;
 #pragma unroll
       for (int m = 0; m < 4; ++m) acc = fmaf(wr[lane + 64 * m], hs[lane + 64 * m], acc);
-      acc = vs_wave_sum(acc);
+      acc = wave_sum(acc);
       if (lane == 0) e[o] = fmaxf(acc + p.bias[o], 0.f);
     }
     __syncthreads();
     const float v = e[t];
-    const float ss = emb_block_sum(v * v, red, t);
+    const float ss = block_sum_pairwise(v * v, red, t);
+    __syncthreads();                                                        // red is written again below
     const float en = v / sqrtf(ss);                                         // no epsilon: an all-zero e gives NaN, as the reference
     if (p.partial) p.partial[slot * LS_H + t] = en;
     sum += en;
   }
   if (p.utt) {
     const float m = sum / (float)cnt;
-    const float ss = emb_block_sum(m * m, red, t);
+    const float ss = block_sum_pairwise(m * m, red, t);
+    __syncthreads();
     p.utt[(long)b * LS_H + t] = m / sqrtf(ss);
   }
 }
 
-static inline size_t ls_align(size_t v) { return (v + 255) & ~(size_t)255; }
 static inline int ls_kp(int K) { return (K + 15) & ~15; }
 
 struct LstmPlan { size_t wih[3], whh[3], xp, hseq, total; long rows0, rowsN; };
@@ -406,12 +373,12 @@ static bool lstm_plan(int B, int F, int I, int P, int T_steps, int layers, LstmP
   if (pl->rows0 > (1L << 21) || pl->rowsN > (1L << 21)) return false;
   size_t off = 0;
   for (int l = 0; l < layers; ++l) {
-    pl->wih[l] = off; off += ls_align((size_t)LS_G * ls_kp(l ? LS_H : I) * 4);
-    pl->whh[l] = off; off += ls_align((size_t)LS_G * LS_H * 4);
+    pl->wih[l] = off; off += tdvc_align256((size_t)LS_G * ls_kp(l ? LS_H : I) * 4);
+    pl->whh[l] = off; off += tdvc_align256((size_t)LS_G * LS_H * 4);
   }
   const long rows = layers > 1 && pl->rowsN > pl->rows0 ? pl->rowsN : pl->rows0;
-  pl->xp = off; off += ls_align((size_t)rows * LS_G * 4);
-  pl->hseq = off; off += layers > 1 ? ls_align((size_t)pl->rowsN * LS_H * 4) : 0;
+  pl->xp = off; off += tdvc_align256((size_t)rows * LS_G * 4);
+  pl->hseq = off; off += layers > 1 ? tdvc_align256((size_t)pl->rowsN * LS_H * 4) : 0;
   pl->total = off;
   return true;
 }
@@ -457,14 +424,14 @@ extern "C" int tdvc_voice_mel(const float* signal, int64_t s_bs, const int32_t* 
   using namespace tdvc;
   if (B < 0 || T < 0 || F < 0 || s_bs < 0 || frame_step < 1) return tdvc_fail(TDVC_EINVAL, "voice_mel: negative B, T, F or stride, frame_step < 1");
   if (!(min_coverage == min_coverage)) return tdvc_fail(TDVC_EINVAL, "voice_mel: min_coverage is NaN");
-  if (!pad_constant && T <= VM_NFFT / 2) return tdvc_fail(TDVC_EUNSUPPORTED, "voice_mel: reflect padding needs T > 200 samples");
+  if (!pad_constant && T <= DFT_NFFT / 2) return tdvc_fail(TDVC_EUNSUPPORTED, "voice_mel: reflect padding needs T > 200 samples");
   if (T > (1 << 26) || frame_step > (1 << 20) || B > 65535) return tdvc_fail(TDVC_EUNSUPPORTED, "voice_mel: T > 2^26, frame_step > 2^20 or B > 65535");
   if (B == 0 || F == 0) return TDVC_OK;
   if (!signal || !tables || !mel) return tdvc_fail(TDVC_EINVAL, "voice_mel: null pointer");
   MelP p;
   p.x = signal; p.x_bs = s_bs; p.lengths = lengths; p.T = T; p.F = F; p.frame_step = frame_step; p.min_cov = min_coverage;
   p.pad_const = pad_constant; p.gain = gain; p.tab = tables; p.out = mel;
-  hipLaunchKernelGGL(voice_mel_kernel, dim3((F + VM_FR - 1) / VM_FR, B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(voice_mel_kernel, dim3((F + DFT_FR - 1) / DFT_FR, B), dim3(256), 0, (hipStream_t)stream, p);
   TDVC_CHECK_LAUNCH();
   return TDVC_OK;
 }

@@ -5,7 +5,7 @@
 // tdvc_dio is seven launches on one stream, none of which waits for the host:
 //   dio_tables_kernel      1 + nb blocks: the low-cut FIR h (2c + 1 taps, its sum in a fixed order) and the nb Nuttall windows
 //   dio_mean_kernel        one block per row: the row mean; per-thread partials in ascending order, a shuffle butterfly per wave, the 4
-//                          wave sums added in order
+//                          wave sums added pairwise (reduce.h)
 //   dio_lowcut_kernel      (tile, row): y = (x - mean) * h, a tile of 1024 outputs and its halo in LDS, 4 consecutive outputs per thread
 //   dio_band_kernel<0>     (tile, band, row): f = y * w_k for 1024 samples with the 4 hal - 1 halo in LDS, then the four kinds of
 //                          events of the tile's first 1022 samples (an event reads f[i .. i + 2]) are COUNTED (at most 511 of a
@@ -34,6 +34,7 @@
 #include "../../include/tdvc.h"
 #include "api_util.h"
 #include "conv_common.h"
+#include "reduce.h"
 
 namespace tdvc {
 
@@ -55,21 +56,14 @@ struct DioP {
   float* f0; long f0_bs;
 };
 
-__device__ __forceinline__ int dio_len(const DioP& p, int b) { return p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T; }
+__device__ __forceinline__ int dio_len(const DioP& p, int b) { return row_len(p.lengths, b, p.T); }
 
-__device__ __forceinline__ double dio_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-// sum over the block of 256 threads, the same value in every thread; red holds 4 doubles. Leaves a barrier behind.
+// sum over the block of 256 threads in every thread; red holds 4 doubles. The barrier before the write protects an earlier use of red.
 __device__ __forceinline__ double dio_block_sum(double v, double* red, int t) {
-  v = dio_wave_sum(v);
+  v = wave_sum(v);
   __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
+  block_stage(v, red, t);
+  return sum_pairwise(red);
 }
 
 __global__ __launch_bounds__(DIO_THREADS) void dio_tables_kernel(DioP p) {
@@ -441,7 +435,7 @@ __device__ double sm_fix(SmLds& s, int t, int wl, int N, double fs, double g, in
   for (int h = 0; h < 6; ++h)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const double v = dio_wave_sum(acc[h][q]);
+      const double v = wave_sum(acc[h][q]);
       if ((t & 63) == 0) s.red[t >> 6][h * 4 + q] = v;
     }
   __syncthreads();
@@ -450,7 +444,7 @@ __device__ double sm_fix(SmLds& s, int t, int wl, int N, double fs, double g, in
   for (int h = 0; h < 6; ++h) {
     if (h >= nh) break;
     double r[4];
-    for (int q = 0; q < 4; ++q) r[q] = (s.red[0][h * 4 + q] + s.red[1][h * 4 + q]) + (s.red[2][h * 4 + q] + s.red[3][h * 4 + q]);
+    for (int q = 0; q < 4; ++q) r[q] = sum_pairwise<24>(&s.red[0][h * 4 + q]);
     const double P = r[0] * r[0] + r[1] * r[1], nm = r[0] * r[3] - r[1] * r[2];
     const double inst = P == 0.0 ? 0.0 : (double)idx[h] * fs / N + nm / P * fs / 2.0 / M_PI;
     const double amp = sqrt(P);
@@ -466,7 +460,7 @@ __global__ __launch_bounds__(DIO_THREADS) void stonemask_kernel(SmP p) {
   const long b = blk / p.F, fr = blk - b * p.F;
   const float fv = p.fi[b * p.fi_bs + fr * p.fi_fs];
   float* o = p.fo + b * p.fo_bs + fr;
-  const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;
+  const int len = p.lengths ? min(max(p.lengths[b], 0), p.T) : p.T;   // row_len, spelled out: as a call the test below compiles differently
   const double fs = p.fs, f = (double)fv;
   if (!isfinite(fv) || f <= 40.0 || f > fs / 12.0 || len <= 0) {             // uniform over the block
     if (t == 0) *o = 0.0f;

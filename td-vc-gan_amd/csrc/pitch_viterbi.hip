@@ -52,7 +52,6 @@ static inline size_t vt_tab_bytes(int n, int W) {
   const int P = vt_parts(n);
   return (size_t)((W + P - 1) / P) * vt_threads(n) * sizeof(float);
 }
-static inline size_t vt_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // larger value wins, the lower index on a tie
 __device__ __forceinline__ void vt_better(float& v, int& i, float v2, int i2) {
@@ -170,10 +169,10 @@ static void launch_viterbi(const VitP& p, int B, int threads, bool tab_lds, size
 }
 
 // workspace layout: predecessors [B][F][n] uint16, then (n large enough that some W <= 256 does not fit the LDS) B table slices
-static inline size_t vt_bp_bytes(int B, int F, int n) { return vt_align((size_t)B * F * n * sizeof(unsigned short)); }
+static inline size_t vt_bp_bytes(int B, int F, int n) { return tdvc_align256((size_t)B * F * n * sizeof(unsigned short)); }
 static inline size_t vt_tab_slice(int n) {
   const size_t worst = vt_tab_bytes(n, VT_MAX_W);
-  return vt_fixed_lds(n) + worst > VT_LDS_BYTES ? vt_align(worst) : 0;
+  return vt_fixed_lds(n) + worst > VT_LDS_BYTES ? tdvc_align256(worst) : 0;
 }
 
 }  // namespace tdvc

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
+#include "reduce.h"
+
 namespace tdvc {
 
 constexpr int YIN_THREADS = 256;
@@ -17,35 +19,12 @@ constexpr int YIN_D_FLOATS = YIN_R * YIN_THREADS; // NC slices x (R * NG) rows, 
 constexpr int YIN_RED_SLOTS = 6;                  // block-reduction slots of YIN_WAVES values each
 constexpr float YIN_FLOOR = 1e-5f;                // floor of the CMDF's denominator
 
-__device__ __forceinline__ int yin_block_min(int v, int* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  int r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r = min(r, red[slot * YIN_WAVES + w]);
-  return r;
-}
-__device__ __forceinline__ float yin_block_minf(float v, float* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  float r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r = fminf(r, red[slot * YIN_WAVES + w]);
-  return r;
-}
+// the block reductions of reduce.h on slot `slot` of red (a slot per reduction: no barrier protects a reuse); the sum adds the wave
+// values left to right
+template <typename T>
+__device__ __forceinline__ T yin_block_min(T v, T* red, int slot) { return block_min<YIN_WAVES>(v, red + slot * YIN_WAVES, threadIdx.x); }
 __device__ __forceinline__ float yin_block_sum(float v, float* red, int slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // butterfly: the same tree in every lane and every run
-  if ((threadIdx.x & 63) == 0) red[slot * YIN_WAVES + (threadIdx.x >> 6)] = v;
-  __syncthreads();
-  float r = red[slot * YIN_WAVES];
-#pragma unroll
-  for (int w = 1; w < YIN_WAVES; ++w) r += red[slot * YIN_WAVES + w];
-  return r;
+  return block_sum_in_order<YIN_WAVES>(v, red + slot * YIN_WAVES, threadIdx.x);
 }
 
 // acc[r] += (a_i - w[i + r])^2 for the four j of one step; W = the seven window values u[j+tau0 .. j+tau0+6]
@@ -195,7 +174,7 @@ __device__ __forceinline__ void yin_soft_search(const float* cl, int n, float* r
   const int tid = threadIdx.x;
   mn = INFINITY;
   for (int k = tid; k < n; k += YIN_THREADS) mn = fminf(mn, cl[k]);
-  mn = yin_block_minf(mn, red, 1);
+  mn = yin_block_min(mn, red, 1);
   se = 0.f; sk = 0.f;
   for (int k = tid; k < n; k += YIN_THREADS) {
     float e = yin_soft_weight(cl[k], mn);

@@ -25,6 +25,7 @@
 
 #include "../../include/tdvc.h"
 #include "api_util.h"
+#include "reduce.h"
 
 namespace tdvc {
 
@@ -34,11 +35,6 @@ constexpr int AT_TQ = 64, AT_TK = 64, AT_MAXT = 4096;
 
 typedef float wl_f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double wl_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 __device__ __forceinline__ float wl_gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ double wl_gelu(double v) { return 0.5 * v * (1.0 + erf(v * 0.70710678118654752440)); }
 
@@ -213,14 +209,14 @@ __global__ __launch_bounds__(256) void wavlm_norm_kernel(NormP p) {
       v[i] = a;
       s += a;
     }
-    const double mean = wl_wave_sum(s) / (double)p.C;
+    const double mean = wave_sum(s) / (double)p.C;
     double ss = 0.0;
 #pragma unroll
     for (int i = 0; i < WL_MAXC / 64; ++i) {
       const double dlt = lane + 64 * i < p.C ? v[i] - mean : 0.0;
       ss = fma(dlt, dlt, ss);
     }
-    const double rstd = 1.0 / sqrt(wl_wave_sum(ss) / (double)p.C + 1e-5);
+    const double rstd = 1.0 / sqrt(wave_sum(ss) / (double)p.C + 1e-5);
     float* yr = p.y + b * p.y_bs + (long)tt * p.y_ts;
 #pragma unroll
     for (int i = 0; i < WL_MAXC / 64; ++i) {

@@ -93,30 +93,17 @@ def fbank_matrix(n_mels=80):
 
 def _tables(device, n_mels):
     """float64 [400 cos | 400 sin | 400 Hamming | n_mels x 201 filterbank] on the device, uploaded once."""
-    def build():
-        i = np.arange(N_FFT, dtype=np.float64)
-        return np.concatenate([np.cos(2.0 * np.pi * i / N_FFT), np.sin(2.0 * np.pi * i / N_FFT), 0.54 - 0.46 * np.cos(2.0 * np.pi * i / N_FFT),
-                               fbank_matrix(n_mels).reshape(-1)])
-    return H.device_table(device, f'ecapa_tables_{n_mels}', build)
+    return H.device_table(device, f'ecapa_tables_{n_mels}',
+                          lambda: np.concatenate([H.dft_tables(N_FFT, (0.54, 0.46)), fbank_matrix(n_mels).reshape(-1)]))
 
 
 # ------------------------------------------------------------------------------------------------------------------ operators
-def _lengths(who, lengths, B, device):
-    if lengths is None:
-        return None
-    lengths = torch.as_tensor(lengths, device=device) if not torch.is_tensor(lengths) else lengths
-    H.need_device(who, lengths)
-    if lengths.shape != (B,):
-        raise ValueError(f'{who}: lengths must be [{B}]')
-    return lengths.to(torch.int32).contiguous()
-
-
 def _fbank(who, signal, lengths, n_mels):
     """-> (feats [B, n_mels, F], frames int32 [B])"""
     H.need_device(who, signal)
     x2, bs, _ = H.rows2(who, signal)
     B, T = x2.shape
-    lengths = _lengths(who, lengths, B, x2.device)
+    lengths = H.device_lengths(who, lengths, B, x2.device)
     n_mels = int(n_mels)
     if n_mels < 16 or n_mels > 128 or n_mels % 16:
         raise ValueError(f'{who}: n_mels must be a multiple of 16 up to 128, got {n_mels}')
@@ -153,13 +140,6 @@ def _act3(who, t):
     return t, (t.stride(0) if B > 1 else Cc * max(t.stride(1), F)), (t.stride(1) if Cc > 1 else F)
 
 
-def _vec(who, t, n):
-    H.need_device(who, t)
-    if t.numel() != n:
-        raise ValueError(f'{who}: a vector of {t.numel()} elements, expected {n}')
-    return t.detach().float().contiguous()
-
-
 def tdnn_fwd(x, weight, bias=None, dilation=1, epilogue=EPI_NONE, scale=None, shift=None, x2=None, row_bias=None, frames=None, out=None):
     """The reflect-padded, length-aware Conv1d (tdvc_tdnn_fwd): x [B, Cin, F] (+ x2, added before the convolution), weight
     [Cout, Cin, K] -> out [B, Cout, F] (given, possibly a channel slice, or new). Frames at and past frames[b] are neither read nor
@@ -186,7 +166,7 @@ def tdnn_fwd(x, weight, bias=None, dilation=1, epilogue=EPI_NONE, scale=None, sh
     keep = [w, x, x2]
     for name, t, n in (('bias', bias, Cout), ('scale', scale, Cout), ('shift', shift, Cout), ('row_bias', row_bias, B * Cout)):
         if t is not None:
-            t = _vec(who, t, n)
+            t = H.vec(who, t, n, name)
             keep.append(t)
             setattr(a, name, t.data_ptr())
     if frames is not None:
@@ -215,8 +195,8 @@ def se_block(x, residual, w1, b1, w2, b2, frames=None, out=None, return_gate=Fal
         raise ValueError(f'{who}: residual must have the shape of x')
     H.need_device(who, w1, w2)
     S = w1.shape[0]
-    w1, w2 = _vec(who, w1, S * Cc), _vec(who, w2, S * Cc)
-    b1, b2 = _vec(who, b1, S), _vec(who, b2, Cc)
+    w1, w2 = H.vec(who, w1, S * Cc), H.vec(who, w2, S * Cc)
+    b1, b2 = H.vec(who, b1, S), H.vec(who, b2, Cc)
     if frames is not None:
         H.need_device(who, frames)
         frames = frames.to(torch.int32).contiguous()
@@ -240,8 +220,8 @@ def asp_pool(x, w_tdnn, b_tdnn, scale, shift, w_conv, b_conv, frames=None):
     B, Cc, F = x.shape
     H.need_device(who, w_tdnn, w_conv)
     A = w_tdnn.shape[0]
-    w_tdnn, w_conv = _vec(who, w_tdnn, A * 3 * Cc), _vec(who, w_conv, A * Cc)
-    b_tdnn, scale, shift, b_conv = _vec(who, b_tdnn, A), _vec(who, scale, A), _vec(who, shift, A), _vec(who, b_conv, Cc)
+    w_tdnn, w_conv = H.vec(who, w_tdnn, A * 3 * Cc), H.vec(who, w_conv, A * Cc)
+    b_tdnn, scale, shift, b_conv = H.vec(who, b_tdnn, A), H.vec(who, scale, A), H.vec(who, shift, A), H.vec(who, b_conv, Cc)
     if frames is not None:
         H.need_device(who, frames)
         frames = frames.to(torch.int32).contiguous()
@@ -264,7 +244,7 @@ def ecapa_head(pooled, scale, shift, weight, bias):
     pooled = pooled.detach().float().contiguous()
     B, N = pooled.shape
     E = weight.shape[0]
-    weight, bias, scale, shift = _vec(who, weight, E * N), _vec(who, bias, E), _vec(who, scale, N), _vec(who, shift, N)
+    weight, bias, scale, shift = H.vec(who, weight, E * N), H.vec(who, bias, E), H.vec(who, scale, N), H.vec(who, shift, N)
     emb = torch.empty(B, E, dtype=torch.float32, device=pooled.device)
     H.check(who, L.lib().tdvc_ecapa_head(pooled.data_ptr(), B, N, scale.data_ptr(), shift.data_ptr(), weight.data_ptr(), bias.data_ptr(), E,
                                          emb.data_ptr(), H.stream(pooled)))

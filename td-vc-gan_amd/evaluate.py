@@ -168,7 +168,7 @@ def _cheaptrick(who, signal, f0, sample_rate, n_fft, hop, q1, lengths, floor, wa
     hop = int(round(sample_rate / 200)) if hop is None else int(hop)
     x, f = signal.detach().float(), f0.detach().float()
     F, nb, dev = f.shape[1], n_fft // 2 + 1, x.device
-    ln = _len_arg(who, lengths, B, dev)
+    ln = H.device_lengths(who, lengths, B, dev, move=True)
     env = torch.empty(B, F, nb, dtype=torch.float32, device=dev) if want_env else None
     mc = mat = None
     order = 0
@@ -230,15 +230,6 @@ def mel_cepstrum(signal, sample_rate=16000, n_fft=1024, hop=80, order=24, alpha=
 
 
 # ------------------------------------------------------------------------------------------------------------ DTW
-def _len_arg(who, v, B, device):
-    if v is None:
-        return None
-    v = torch.as_tensor(v, device=device) if not torch.is_tensor(v) else v.to(device)
-    if v.shape != (B,):
-        raise ValueError(f'{who}: lengths must be [{B}]')
-    return v.to(torch.int32).contiguous()
-
-
 def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
     """Exact dynamic time warping of x [B, N, D] against y [B, M, D] (device fp32; [N, D] / [M, D] for one pair) ->
     (cost float64 [B], length int32 [B][, path int64 [B, N + M - 1, 2]]); tdvc_dtw, one launch, no host synchronisation.
@@ -260,7 +251,7 @@ def dtw(x, y, x_len=None, y_len=None, metric='l2', return_path=False):
         raise ValueError(f'dtw: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in batch or feature size')
     M = y3.shape[1]
     dev = x3.device
-    xl, yl = _len_arg('dtw', x_len, B, dev), _len_arg('dtw', y_len, B, dev)
+    xl, yl = H.device_lengths('dtw', x_len, B, dev, move=True), H.device_lengths('dtw', y_len, B, dev, move=True)
     lib = L.lib()
     cost = torch.empty(B, dtype=torch.float64, device=dev)
     length = torch.empty(B, dtype=torch.int32, device=dev)
@@ -299,7 +290,7 @@ def fastdtw(x, y, x_len=None, y_len=None, radius=1, metric='l2', return_path=Fal
         raise ValueError(f'fastdtw: x {tuple(x3.shape)} and y {tuple(y3.shape)} differ in batch or feature size')
     M = y3.shape[1]
     dev = x3.device
-    xl, yl = _len_arg('fastdtw', x_len, B, dev), _len_arg('fastdtw', y_len, B, dev)
+    xl, yl = H.device_lengths('fastdtw', x_len, B, dev, move=True), H.device_lengths('fastdtw', y_len, B, dev, move=True)
     lib = L.lib()
     cost = torch.empty(B, dtype=torch.float64, device=dev)
     length = torch.empty(B, dtype=torch.int32, device=dev)

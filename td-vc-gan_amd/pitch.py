@@ -236,12 +236,7 @@ def track_f0(signal, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, thr
 def _world_rows(who, signal, lengths):
     H.need_device(who, signal)
     x2, x_bs, lead = H.rows2(who, signal)
-    if lengths is not None:
-        lengths = torch.as_tensor(lengths, device=x2.device) if not torch.is_tensor(lengths) else lengths.to(x2.device)
-        if lengths.numel() != x2.shape[0]:
-            raise ValueError(f'{who}: lengths must hold one entry per row ({x2.shape[0]})')
-        lengths = lengths.reshape(-1).to(torch.int32).contiguous()
-    return x2, x_bs, lead, lengths
+    return x2, x_bs, lead, H.device_lengths(who, lengths, x2.shape[0], x2.device, move=True, any_shape=True)
 
 
 def dio(signal, sample_rate=16000, hop=80, f0_floor=50.0, f0_ceil=500.0, channels_in_octave=2.0, allowed_range=0.1, lengths=None,

@@ -73,11 +73,7 @@ def mel_filterbank():
 
 def _tables(device):
     """float64 [400 cos | 400 sin | 400 Hann | 40 x 201 filterbank] on the device, uploaded once."""
-    def build():
-        i = np.arange(N_FFT, dtype=np.float64)
-        return np.concatenate([np.cos(2.0 * np.pi * i / N_FFT), np.sin(2.0 * np.pi * i / N_FFT), 0.5 - 0.5 * np.cos(2.0 * np.pi * i / N_FFT),
-                               mel_filterbank().reshape(-1)])
-    return H.device_table(device, 'speaker_tables', build)
+    return H.device_table(device, 'speaker_tables', lambda: np.concatenate([H.dft_tables(N_FFT, (0.5, 0.5)), mel_filterbank().reshape(-1)]))
 
 
 def frame_step(rate=1.3):
@@ -122,16 +118,6 @@ def window_count(n_samples, rate=1.3, min_coverage=0.75):
 
 
 # ------------------------------------------------------------------------------------------------------------------ operators
-def _lengths(who, lengths, B, device):
-    if lengths is None:
-        return None
-    lengths = torch.as_tensor(lengths, device=device) if not torch.is_tensor(lengths) else lengths
-    H.need_device(who, lengths)
-    if lengths.shape != (B,):
-        raise ValueError(f'{who}: lengths must be [{B}]')
-    return lengths.to(torch.int32).contiguous()
-
-
 def _front(who, signal, lengths, rate, min_coverage, normalize, pad_mode):
     """-> (mel [B, F, 40], lengths int32 or None, frame step, P_max)"""
     H.need_device(who, signal)
@@ -141,7 +127,7 @@ def _front(who, signal, lengths, rate, min_coverage, normalize, pad_mode):
         raise ValueError(f'{who}: min_coverage is NaN')
     x2, bs, _ = H.rows2(who, signal)
     B, T = x2.shape
-    lengths = _lengths(who, lengths, B, x2.device)
+    lengths = H.device_lengths(who, lengths, B, x2.device)
     step = frame_step(rate)
     if pad_mode == 'reflect' and T <= N_FFT // 2:
         raise ValueError(f'{who}: reflect padding needs T > 200 samples')

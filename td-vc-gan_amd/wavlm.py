@@ -144,13 +144,6 @@ def _tok3(who, t, name='x'):
     return t, (t.stride(0) if B > 1 else max(T, 1) * ts), ts
 
 
-def _vec(who, t, n, name):
-    H.need_device(who, t)
-    if t.numel() != n:
-        raise ValueError(f'{who}: {name} has {t.numel()} elements, expected {n}')
-    return t.detach().float().contiguous().reshape(-1)
-
-
 def _gemm(who, B, T, N, K, x, x_bs, x_ts, w, bias, y, y_bs, y_ts, epilogue=EPI_NONE, res=None, r_bs=0, r_ts=0, scale=None, dev=None):
     a = L.WavlmGemmArgs()
     a.B, a.T, a.N, a.K, a.groups, a.seg_len, a.epilogue = B, T, N, K, 1, 0, int(epilogue)
@@ -181,7 +174,7 @@ def wavlm_gemm(x, weight, bias=None, epilogue=EPI_NONE, residual=None, out=None,
     if T < kernel:
         raise ValueError(f'{who}: {T} tokens are fewer than the kernel {kernel}')
     N, To = weight.shape[0], (T - kernel) // stride + 1
-    bias = None if bias is None else _vec(who, bias, N, 'bias')
+    bias = None if bias is None else H.vec(who, bias, N, 'bias')
     if out is None:
         out = torch.empty(B, To, N, dtype=torch.float32, device=x.device)
     out, y_bs, y_ts = _tok3(who, out, 'out')
@@ -210,7 +203,7 @@ def wavlm_conv0(signal, weight_t, gamma, beta, stride, out=None):
     if Ln < k:
         raise ValueError(f'{who}: a row of {Ln} samples is shorter than the kernel {k}')
     T = (Ln - k) // int(stride) + 1
-    gamma, beta = _vec(who, gamma, Cc, 'gamma'), _vec(who, beta, Cc, 'beta')
+    gamma, beta = H.vec(who, gamma, Cc, 'gamma'), H.vec(who, beta, Cc, 'beta')
     if out is None:
         out = torch.empty(B, T, Cc, dtype=torch.float32, device=x2.device)
     out, y_bs, y_ts = _tok3(who, out, 'out')
@@ -227,7 +220,7 @@ def wavlm_layernorm(x, gamma, beta, gelu=False, out=None, grep=None):
     who = 'wavlm_layernorm'
     x, x_bs, x_ts = _tok3(who, x)
     B, T, Cc = x.shape
-    gamma, beta = _vec(who, gamma, Cc, 'gamma'), _vec(who, beta, Cc, 'beta')
+    gamma, beta = H.vec(who, gamma, Cc, 'gamma'), H.vec(who, beta, Cc, 'beta')
     if out is None:
         out = torch.empty(B, T, Cc, dtype=torch.float32, device=x.device)
     out, y_bs, y_ts = _tok3(who, out, 'out')
@@ -238,7 +231,7 @@ def wavlm_layernorm(x, gamma, beta, gelu=False, out=None, grep=None):
         Hh = grep[2].numel()
         if Hh < 1 or Cc % Hh:
             raise ValueError(f'{who}: {Cc} channels do not divide into {Hh} heads')
-        gw, gb, ga = _vec(who, grep[0], 8 * (Cc // Hh), 'grep_linear.weight'), _vec(who, grep[1], 8, 'grep_linear.bias'), _vec(who, grep[2], Hh, 'grep_a')
+        gw, gb, ga = H.vec(who, grep[0], 8 * (Cc // Hh), 'grep_linear.weight'), H.vec(who, grep[1], 8, 'grep_linear.bias'), H.vec(who, grep[2], Hh, 'grep_a')
         gate = torch.empty(B, Hh, T, dtype=torch.float32, device=x.device)
     H.check(who, L.lib().tdvc_wavlm_layernorm(x.data_ptr(), x_bs, x_ts, B, T, Cc, gamma.data_ptr(), beta.data_ptr(), int(bool(gelu)), out.data_ptr(),
                                               y_bs, y_ts, Hh, H.ptr(gw), H.ptr(gb), H.ptr(ga), H.ptr(gate), H.stream(x)))
@@ -258,7 +251,7 @@ def wavlm_posconv(xp, weight, bias, kernel, groups, out=None):
     H.need_device(who, weight)
     if weight.dtype != torch.float32 or not weight.is_contiguous() or groups < 1 or Cc % groups or tuple(weight.shape) != (Cc, kernel, Cc // groups):
         raise ValueError(f'{who}: weight must be contiguous fp32 [{Cc}, {kernel}, C / groups], got {tuple(weight.shape)}')
-    bias = _vec(who, bias, Cc, 'bias')
+    bias = H.vec(who, bias, Cc, 'bias')
     if out is None:
         out = torch.empty(B, T, Cc, dtype=torch.float32, device=xp.device)
     out, y_bs, y_ts = _tok3(who, out, 'out')

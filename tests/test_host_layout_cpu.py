@@ -1,6 +1,6 @@
 """CPU: the host-side layer of the operator wrappers (td-vc-gan_amd/_host.py): which layouts reach a kernel as views and which as
-dense copies, the strides reported for them, the autograd path of the YIN flavour, the shape and device errors, and the table
-cache. Pure torch stride logic: no GPU and no built library."""
+dense copies, the strides reported for them, the autograd path of the YIN flavour, the shape and device errors, the per-row
+lengths and parameter vectors, and the table cache. Pure torch stride logic: no GPU and no built library."""
 import importlib
 
 import numpy as np
@@ -179,6 +179,81 @@ def test_need_device_has_no_cpu_fallback():
             H.need_device('resample', *bad)
         assert 'resample' in str(e.value)
     H.need_device('resample')                                      # nothing to check
+
+
+def test_device_lengths_strict():
+    """What speaker and ecapa take: None stays None, a tensor must be on a device already, the shape is (B,)."""
+    H = host()
+    Err = pkg()._lib.TdvcError
+    assert H.device_lengths('fbank', None, B, 'cpu') is None
+    assert H.device_lengths('fbank', None, B, 'cpu', move=True, any_shape=True) is None
+    for bad in (torch.tensor([5, 4, 3]), torch.tensor([5, 4, 3, 2]), torch.tensor([[5], [4], [3]])):
+        with pytest.raises(Err, match='no CPU fallback') as e:                           # before any shape check
+            H.device_lengths('fbank', bad, B, 'cpu')
+        assert 'fbank' in str(e.value)
+
+
+def test_device_lengths_moving():
+    """What evaluate and pitch take: a tensor on another device is moved, the values arrive as int32 [B], contiguous."""
+    H = host()
+    want = torch.tensor([5, 0, 3], dtype=torch.int32)
+    wide = torch.tensor([5, 9, 0, 9, 3, 9])
+    cases = {'list': [5, 0, 3], 'tuple': (5, 0, 3), 'numpy': np.array([5, 0, 3]), 'int64 tensor': torch.tensor([5, 0, 3]),
+             'int32 tensor': want.clone(), 'strided view': wide[::2]}
+    for name, v in cases.items():
+        for kw in ({'move': True}, {'move': True, 'any_shape': True}):
+            r = H.device_lengths('dtw', v, B, 'cpu', **kw)
+            assert r.dtype == torch.int32 and r.shape == (B,) and r.is_contiguous() and r.stride() == (1,) and torch.equal(r, want), name
+    assert torch.equal(wide, torch.tensor([5, 9, 0, 9, 3, 9]))                           # the caller's tensor is left alone
+    big = H.device_lengths('dtw', torch.tensor([2 ** 31 - 1, 0, 1]), B, 'cpu', move=True)
+    assert big.tolist() == [2 ** 31 - 1, 0, 1]
+
+
+def test_device_lengths_shapes():
+    H = host()
+    for bad in ([5, 4], [5, 4, 3, 2], torch.tensor([5, 4]), torch.zeros(B + 1, dtype=torch.int64), torch.tensor(5)):
+        for kw in ({'move': True}, {'move': True, 'any_shape': True}):
+            with pytest.raises(ValueError, match='dio') as e:
+                H.device_lengths('dio', bad, B, 'cpu', **kw)
+            assert f'[{B}]' in str(e.value)
+    col = torch.tensor([[5], [0], [3]])
+    for v in (col, col.tolist(), col.reshape(1, B), torch.tensor([5, 9, 0, 9, 3, 9]).reshape(B, 2)[:, :1]):
+        r = H.device_lengths('dio', v, B, 'cpu', move=True, any_shape=True)
+        assert r.shape == (B,) and r.dtype == torch.int32 and r.is_contiguous() and r.tolist() == [5, 0, 3]
+        with pytest.raises(ValueError, match='dio'):                                     # the default wants [B] itself
+            H.device_lengths('dio', v, B, 'cpu', move=True)
+
+
+def test_vec():
+    """A CPU has no device tensor to flatten: what can be pinned here is that nothing else gets through, and what the message names."""
+    H = host()
+    Err = pkg()._lib.TdvcError
+    for bad in (torch.zeros(4), torch.zeros(2, 2), None, np.zeros(4), [0.0] * 4):
+        with pytest.raises(Err, match='no CPU fallback') as e:
+            H.vec('layer_norm', bad, 4, 'gamma')
+        assert 'layer_norm' in str(e.value)
+    with pytest.raises(Err):                                                             # the device check comes before the count
+        H.vec('layer_norm', torch.zeros(5), 4)
+
+
+def test_dft_tables():
+    H = host()
+    n = 8
+    i = np.arange(n, dtype=np.float64)
+    t = H.dft_tables(n, (0.54, 0.46))
+    assert t.dtype == np.float64 and t.shape == (3 * n,)
+    assert np.array_equal(t[:n], np.cos(2.0 * np.pi * i / n)) and np.array_equal(t[n:2 * n], np.sin(2.0 * np.pi * i / n))
+    assert np.array_equal(t[2 * n:], 0.54 - 0.46 * np.cos(2.0 * np.pi * i / n))
+    w = np.linspace(0.0, 1.0, n)
+    for given in (w, w.tolist(), w.astype(np.float32)):
+        u = H.dft_tables(n, given)
+        assert u.dtype == np.float64 and np.array_equal(u[:2 * n], t[:2 * n]) and np.array_equal(u[2 * n:], np.asarray(given, dtype=np.float64))
+    for bad in (w[:-1], (0.5, 0.5, 0.5)):
+        with pytest.raises(ValueError):
+            H.dft_tables(n, bad)
+    P = pkg()
+    for tab, fb, win in ((P.speaker, P.speaker.mel_filterbank(), (0.5, 0.5)), (P.ecapa, P.ecapa.fbank_matrix(16), (0.54, 0.46))):
+        assert fb.shape[1] == 201 and H.dft_tables(tab.N_FFT, win).shape == (1200,)
 
 
 def test_small_helpers():
