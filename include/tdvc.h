@@ -882,6 +882,78 @@ int tdvc_wavlm_posconv(const float* xp, int64_t xp_bs, int32_t B, int32_t T, int
 int tdvc_wavlm_attention(const float* q, const float* k, const float* v, int64_t bs, int64_t ts, int32_t B, int32_t T, int32_t H, int32_t d,
                          const float* gate, const float* bias_rel, float* out, int64_t o_bs, int64_t o_ts, void* stream);
 
+/* The CREPE pitch tracker (csrc/pitch_crepe.hip): what the reference's util/crepe.py filtered_pitch computes with torchcrepe's `tiny`
+ * network at hop 64 (train.py:239, :549, :635; generate_with_target.py:139, :161 with "viterbi"; generate_from_list.py:101, :104),
+ * restated here from torchcrepe's published source. torchcrepe is not available and no weights are shipped: this definition is the
+ * contract and tests/crepe_ref.py restates it in float64 with stock torch ops. PARITY WITH AN INSTALLED TORCHCREPE AND WITH ITS
+ * SHIPPED tiny.pth IS UNCHECKED, and so are the state-dict keys against a real file and `full` beyond one row. Forward only.
+ *   Constants: 360 bins of 20 cents; cents(bin) = 20 bin + 1997.3794084376191; hz(cents) = 10 2^(cents / 1200);
+ *     bin(hz, q) = q((1200 log2(hz / 10) - 1997.3794084376191) / 20), q = floor unless stated; sample rate 16000, window 1024.
+ *   Front end (preprocess, pad=True): the row of n samples is zero-padded by 512 on both sides; F = 1 + n / hop frames (integer
+ *     division) of 1024 samples every hop samples; each frame loses its mean and is divided by max(1e-10, std), std the unbiased
+ *     (n - 1) standard deviation.
+ *   Network (capacity tiny | full): output channels [128, 16, 16, 16, 32, 64] | [1024, 128, 128, 128, 256, 512]; six layers, each
+ *     zero-pad -> conv -> ReLU -> BatchNorm in eval mode (eps 0.0010000000474974513) -> max-pool 2. Layer 1: 1 -> C1, kernel 512,
+ *     stride 4, pad (254, 254): 1024 -> 256 -> 128 positions. Layers 2..6: kernel 64, stride 1, pad (31, 32): 128 -> 64 -> 32 -> 16 ->
+ *     8 -> 4 positions after each pool. THE BATCHNORM COMES AFTER THE RELU AND ITS SCALE MAY BE NEGATIVE: the pool cannot be moved in
+ *     front of the affine. The result [N][C6][4] is flattened POSITION-MAJOR (permute(0, 2, 1): feature l C6 + c), then
+ *     Linear(4 C6, 360) and a sigmoid.
+ *   Post-processing (postprocess and util/crepe.py:55-84) on activations [B][360][F]: bins below minidx = bin(fmin) and from maxidx =
+ *     bin(fmax, ceil) on are excluded (39 and 248 for the reference's 50 and 550 Hz; evaluated on the host in float64).
+ *     argmax: the LOWEST index among equal maxima, pitch hz(cents(bin)).
+ *     weighted_argmax: around the argmax bin b the window [max(0, b - 4), min(360, b + 5)); weights sigmoid(activation) inside the
+ *       window and in range, 0 elsewhere (torchcrepe's second sigmoid on values that are already probabilities, kept); pitch
+ *       hz(sum w cents / sum w).
+ *     viterbi: observation = log-softmax over the in-range bins; transition max(12 - |i - j|, 0) row-normalised over all 360 bins;
+ *       uniform initial distribution; decoded by tdvc_viterbi_path on the maxidx - minidx in-range states with jump = +INFINITY; pitch
+ *       hz(cents(bin)) of the path. This equals librosa's programme whenever that avoids its `tiny`-floored transitions, which it
+ *       always does: staying on a state is always possible at finite cost.
+ *     periodicity = the activation at the chosen bin; pitch = 0 where periodicity < threshold (0.21).
+ *     get_shift(src, tgt) = bin(tgt) - bin(src).
+ *   STATED DEVIATION: torchcrepe adds a random triangular dither of +-20 cents to every bin -> cents conversion; here the conversion is
+ *     deterministic (the dither's mean).
+ *   Decisions where the source leaves room: a row with per-row lengths is framed as if it were alone (samples at and past its length
+ *     count as zero and are never read); its frames past 1 + length / hop are zero frames, their activations are those of a zero frame,
+ *     and the decoders give pitch 0 and periodicity 0 there. The comparison with the threshold is made in fp32.
+ * tdvc_crepe_frames: signal [B] rows of T samples (row stride s_bs), lengths device int32 [B] or NULL -> frames fp32 [B][F][1024], F = 1 +
+ *   T / hop. Mean and standard deviation in float64 (two passes; per-wave butterflies, the four waves combined pairwise), one rounding
+ *   at the store. A constant frame gives exactly 0.
+ * tdvc_crepe_conv: one layer, x [N][Cin][Lin] -> y [N][Cout][Lc / 2] dense, Lc = 256 for (Cin 1, K 512, stride 4, Lin 1024), Lc = Lin
+ *   for (K 64, stride 1, Lin in {128, 64, 32, 16, 8}); w [Cout][Cin][K]; y = maxpool2(relu(conv(x) + bias) scale + shift), scale =
+ *   gamma / sqrt(var + eps), shift = beta - mean scale (evaluated in float64 on the host and rounded once). An implicit GEMM on
+ *   v_mfma_f32_16x16x4_f32 (exact fp32): 16 output channels x 256 (frame, position) columns per workgroup, chunks of 128 products
+ *   summed from zero and then accumulated. y must not overlap x.
+ * tdvc_crepe_head: x [N][C][P] -> act[n / F][o][n % F] = sigmoid(sum_{l, c} w[o][l C + c] x[n][c][l] + bias[o]), w [O][P C]; N a
+ *   multiple of F (F = 1: act [N][O]). Float64 sums in a fixed order, one rounding.
+ * tdvc_crepe_decode: act at p[b a_bs + k a_cs + f]; the in-range bins are [lo, hi). mode TDVC_CREPE_ARGMAX / TDVC_CREPE_WEIGHTED write
+ *   pitch and periodicity fp32 [B][F]; `bins` (device int32 [B][F] or NULL, mode ARGMAX only; clamped into [lo, hi)) replaces the
+ *   kernel's own argmax (the Viterbi path); `frames` (device int32 [B] or NULL, clamped to [0, F]): frames at and past it give 0, 0.
+ *   mode TDVC_CREPE_LATTICE writes lattice fp32 [B][F][hi - lo] = act - logsumexp over [lo, hi) (float64 inside, one rounding) and
+ *   ignores frames, bins, pitch and periodicity. Cents -> Hz in float64, rounded once.
+ * Every entry takes a stream; no atomics, fixed summation orders: bit-identical from call to call; no allocation, no host
+ * synchronisation, graph-capturable. TDVC_EINVAL: negative sizes or strides, null pointers, F != 1 + T / hop, N not a multiple of F, an
+ * unknown mode, bins with another mode than ARGMAX, a bin stride below F, conv weights that are not 16-byte aligned.
+ * TDVC_EUNSUPPORTED: hop < 1, a row with no sample (T < 1), B > 65535, T > 2^28, a conv geometry other than the two above, Cout or (K
+ * 64) Cin not a multiple of 16, head C not a multiple of 16 or O of 4, more than 2^16 output channels, 2^22 frames or 2^31 elements
+ * of one operand, an empty bin range or one that leaves [0, n_bins), more than 4096 bins, F > 2^24. All before any launch; B == 0 /
+ * N == 0 is a no-op. */
+enum { TDVC_CREPE_ARGMAX = 0, TDVC_CREPE_WEIGHTED = 1, TDVC_CREPE_LATTICE = 2 };
+typedef struct {
+  int32_t N, Cin, Cout, Lin, K, stride, reserved0, reserved1;
+  const float* x;                             /* [N][Cin][Lin] */
+  const float* w;                             /* [Cout][Cin][K] */
+  const float* bias; const float* scale; const float* shift;      /* [Cout] */
+  float* y;                                   /* [N][Cout][Lc / 2] */
+} tdvc_crepe_conv_args;
+int tdvc_crepe_frames(const float* signal, int64_t s_bs, const int32_t* lengths, int32_t T, int32_t B, int32_t hop, int32_t F,
+                      float* frames, void* stream);
+int tdvc_crepe_conv(const tdvc_crepe_conv_args* args, void* stream);
+int tdvc_crepe_head(const float* x, int32_t N, int32_t C, int32_t P, const float* w, const float* bias, int32_t O, int32_t F,
+                    float* act, void* stream);
+int tdvc_crepe_decode(const float* act, int64_t a_bs, int64_t a_cs, int32_t B, int32_t F, int32_t n_bins, int32_t lo, int32_t hi,
+                      int32_t mode, float threshold, const int32_t* frames, const int32_t* bins, float* pitch, float* periodicity,
+                      float* lattice, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

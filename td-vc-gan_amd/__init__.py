@@ -14,7 +14,9 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     window_count / speaker_similarity (speaker.py), and the speechbrain speaker recognition of
     test_scripts/mls-pt/test_speaker_rec.py (Fbank features, the ECAPA-TDNN embedding, the cosine classifier) as EcapaTdnn /
     load_ecapa / fbank / fbank_matrix / speaker_classify / running_mean_norm (ecapa.py), and the WavLM feature extractor that
-    model/ssl_encoder.py injects into SSLEncoder (wavlm/WavLM.py extract_features) as WavLM / WavLMConfig / load_wavlm (wavlm.py).
+    model/ssl_encoder.py injects into SSLEncoder (wavlm/WavLM.py extract_features) as WavLM / WavLMConfig / load_wavlm (wavlm.py), and
+    the CREPE pitch tracker of util/crepe.py (torchcrepe's tiny / full network, its front end and its argmax, weighted-argmax and
+    Viterbi decoders) as Crepe / load_crepe / crepe_frames / crepe_decode / crepe_transition / get_shift (crepe.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -29,7 +31,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', 'wavlm', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', 'wavlm', 'crepe', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -47,6 +49,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.ecapa'), name)
     if name in ('WavLM', 'WavLMConfig', 'load_wavlm'):
         return getattr(importlib.import_module(f'{__name__}.wavlm'), name)
+    if name in ('Crepe', 'load_crepe', 'crepe_frames', 'crepe_conv', 'crepe_head', 'crepe_decode', 'crepe_lattice', 'crepe_transition', 'get_shift'):
+        return getattr(importlib.import_module(f'{__name__}.crepe'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

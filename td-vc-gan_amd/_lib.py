@@ -86,6 +86,12 @@ class WavlmGemmArgs(C.Structure):
                 ('y', C.c_void_p), ('y_bs', C.c_int64), ('y_ts', C.c_int64)]
 
 
+class CrepeConvArgs(C.Structure):
+    _fields_ = [('N', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('Lin', C.c_int32), ('K', C.c_int32), ('stride', C.c_int32),
+                ('reserved0', C.c_int32), ('reserved1', C.c_int32), ('x', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p),
+                ('scale', C.c_void_p), ('shift', C.c_void_p), ('y', C.c_void_p)]
+
+
 class L1Pair(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('da', C.c_void_p), ('n', C.c_int64), ('weight', C.c_float)]
 
@@ -104,6 +110,7 @@ DG_PLAIN, DG_MASK_LRELU, DG_FILM = 0, 1, 2
 DTW_L2, DTW_L1, DTW_SQ = 0, 1, 2      # tdvc_dtw metric (include/tdvc.h)
 TDNN_NONE, TDNN_RELU_BN, TDNN_RELU_BN_TANH = 0, 1, 2      # tdvc_tdnn_fwd epilogue (include/tdvc.h)
 WAVLM_NONE, WAVLM_GELU = 0, 1      # tdvc_wavlm_gemm epilogue (include/tdvc.h)
+CREPE_ARGMAX, CREPE_WEIGHTED, CREPE_LATTICE = 0, 1, 2      # tdvc_crepe_decode mode (include/tdvc.h)
 RESAMPLE_TO = 256      # outputs per block of tdvc_resample (= tdvc_resample_tile(), csrc/audio_resample.hip RS_TO)
 
 # name -> (restype, argtypes); every symbol include/tdvc.h declares
@@ -232,6 +239,11 @@ SIGNATURES = {
                                   _vp, _vp]),
     'tdvc_wavlm_posconv': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _i64, _vp]),
     'tdvc_wavlm_attention': (_i, [_vp, _vp, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'tdvc_crepe_frames': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    'tdvc_crepe_conv': (_i, [C.POINTER(CrepeConvArgs), _vp]),
+    'tdvc_crepe_head': (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    'tdvc_crepe_decode': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp, _vp, _vp,
+                               _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

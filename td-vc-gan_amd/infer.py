@@ -3,8 +3,9 @@ same kernels as the train step — checkpoint interchange (`step{E}-G.pt` / `lat
 reference's keys), F0 tracking on the device (YIN, pitch.py), log-F0 mean shift towards the target speaker, excitation on the
 device, one whole-utterance forward.
 
-`convert_audio` goes from waveform to waveform: `pitch.track_f0` -> F0 scaling -> `convert`. `convert` still takes an F0 track, so a
-caller with a tracker of its own (the reference's CREPE, util/crepe.py) passes that track in. Audio I/O stays with the caller.
+`convert_audio` goes from waveform to waveform: `pitch.track_f0` -> F0 scaling -> `convert`, or with `f0_tracker=` a `crepe.Crepe`
+the reference's own CREPE tracker (util/crepe.py filtered_pitch(signal, "viterbi")) in place of YIN. `convert` still takes an F0
+track, so a caller with another tracker passes that track in. Audio I/O stays with the caller.
 """
 import torch
 
@@ -62,11 +63,25 @@ def convert(G, signal, c_tgt, f0_conv, noise=None, start_phase=None):
 
 
 @torch.no_grad()
-def convert_audio(G, signal, c_tgt, f0_ratio=1.0, noise=None, start_phase=None, **track_kwargs):
+def convert_audio(G, signal, c_tgt, f0_ratio=1.0, noise=None, start_phase=None, f0_tracker=None, target_signal=None, **track_kwargs):
     """Waveform in, waveform out: the F0 track of `signal` [1, 1, T] from `pitch.track_f0` (track_kwargs: hop, sample_rate, pitch_min,
     pitch_max, threshold, decoder, octave_cost, jump_cost), scaled by f0_ratio (the target / source mean-F0 ratio, train.py:636), then
     `convert`. decoder='viterbi' decodes the track over time, as the reference's inference scripts do (generate_with_target.py:139,
     util.crepe.filtered_pitch(signal, "viterbi")); the default is the per-frame decision. For the log-F0 mean shift instead, call
-    `track_f0` on both speakers, `shift_f0`, and `convert`."""
-    f0_conv = track_f0(signal, **track_kwargs) * f0_ratio
+    `track_f0` on both speakers, `shift_f0`, and `convert`.
+    f0_tracker: a `crepe.Crepe` replaces YIN by the reference's own tracker, `f0_tracker.filtered_pitch(signal, 'viterbi')`
+    (generate_with_target.py:139); with `target_signal` [1, 1, T'] the target speaker's utterance is tracked the same way (:161) and
+    the source contour gets the log-F0 mean shift of `shift_f0` towards it (:163-165) before f0_ratio is applied. track_kwargs belong
+    to YIN and are refused with a tracker; target_signal needs one. With f0_tracker=None nothing changes."""
+    if f0_tracker is None:
+        if target_signal is not None:
+            raise ValueError('convert_audio: target_signal needs f0_tracker (or call track_f0, shift_f0 and convert)')
+        f0_conv = track_f0(signal, **track_kwargs) * f0_ratio
+    else:
+        if track_kwargs:
+            raise ValueError(f'convert_audio: {sorted(track_kwargs)} are arguments of track_f0 and do not apply to f0_tracker')
+        f0_conv, _ = f0_tracker.filtered_pitch(signal, 'viterbi')
+        if target_signal is not None:
+            f0_conv = shift_f0(f0_conv, f0_tracker.filtered_pitch(target_signal, 'viterbi')[0])
+        f0_conv = f0_conv * f0_ratio
     return convert(G, signal, c_tgt, f0_conv, noise=noise, start_phase=start_phase)

@@ -13,7 +13,8 @@ search is piecewise constant and the CMDF of `return_cmdf=True` is a diagnostic 
 util.crepe.filtered_pitch(signal, "viterbi") (generate_with_target.py:139), whose torchcrepe decoder is a max-sum dynamic programme
 with a triangular +-240 cent transition. Here the lattice is the CMDF the YIN launch already produces, decoded by
 tdvc_viterbi_path (csrc/pitch_viterbi.hip); `viterbi_transition` builds the band table and `viterbi_path` is the raw decoder for a
-caller with a lattice of its own (CREPE activations included).
+caller with a lattice of its own; crepe.py is one: `crepe.crepe_decode(decoder='viterbi')` decodes the CREPE network's activations with
+it, which is the reference's call itself (`crepe.Crepe.filtered_pitch(signal, 'viterbi')`).
 
 `dio`, `stonemask` and `world_f0` are WORLD's F0 estimator and its refinement, the pyworld.dio + pyworld.stonemask step of the
 reference's objective evaluation (test_scripts/common/test_mcd.py world_analyze), as HIP kernels in float64 (csrc/pitch_dio.hip,
@@ -209,7 +210,7 @@ def yin_f0(signal, sample_rate, pitch_min=20, pitch_max=20000, frame_stride=0.01
 def track_f0(signal, hop=64, sample_rate=16000, pitch_min=60, pitch_max=500, threshold=0.1, soft=False, decoder=None, octave_cost=1.0,
              jump_cost=16.0):
     """signal [B, 1, T] -> F0 track [B, 1, T // hop + 1] in Hz, 0 = unvoiced: the frame count of the reference's CREPE front end
-    (pad=True), which is what `infer.convert`, `infer.shift_f0` and `TrainStep` take. YIN yields T // hop frames for an utterance
+    (pad=True; `crepe.Crepe.filtered_pitch` is that tracker itself), which is what `infer.convert`, `infer.shift_f0` and `TrainStep` take. YIN yields T // hop frames for an utterance
     of whole hops, so the last frame is repeated once; `f0_to_excitation` drops that frame, as the reference does.
     soft=True selects the softmax-weighted period, differentiable with respect to a signal that requires grad.
     decoder='viterbi' (the reference's inference setting, generate_with_target.py:139) decodes the lag over time: the best path
