@@ -886,7 +886,8 @@ int tdvc_wavlm_attention(const float* q, const float* k, const float* v, int64_t
  * network at hop 64 (train.py:239, :549, :635; generate_with_target.py:139, :161 with "viterbi"; generate_from_list.py:101, :104),
  * restated here from torchcrepe's published source. torchcrepe is not available and no weights are shipped: this definition is the
  * contract and tests/crepe_ref.py restates it in float64 with stock torch ops. PARITY WITH AN INSTALLED TORCHCREPE AND WITH ITS
- * SHIPPED tiny.pth IS UNCHECKED, and so are the state-dict keys against a real file and `full` beyond one row. Forward only.
+ * SHIPPED tiny.pth IS UNCHECKED, and so are the state-dict keys against a real file and `full` beyond one row. The forward; the backward
+ * with respect to the signal follows below.
  *   Constants: 360 bins of 20 cents; cents(bin) = 20 bin + 1997.3794084376191; hz(cents) = 10 2^(cents / 1200);
  *     bin(hz, q) = q((1200 log2(hz / 10) - 1997.3794084376191) / 20), q = floor unless stated; sample rate 16000, window 1024.
  *   Front end (preprocess, pad=True): the row of n samples is zero-padded by 512 on both sides; F = 1 + n / hop frames (integer
@@ -953,6 +954,53 @@ int tdvc_crepe_head(const float* x, int32_t N, int32_t C, int32_t P, const float
 int tdvc_crepe_decode(const float* act, int64_t a_bs, int64_t a_cs, int32_t B, int32_t F, int32_t n_bins, int32_t lo, int32_t hi,
                       int32_t mode, float threshold, const int32_t* frames, const int32_t* bins, float* pitch, float* periodicity,
                       float* lattice, void* stream);
+
+/* The backward of the CREPE tracker with respect to the signal (csrc/pitch_crepe_bwd.hip; tdvc_crepe_conv_train in pitch_crepe.hip): the
+ * reference's activation-MSE F0 term, train.py:439-470, g_loss_f0 = mse(activations(fake), target activations). The network is fixed:
+ * no weight gradient. Nothing of the forward is kept but the pooling decisions and the final activations.
+ * tdvc_crepe_conv_train: tdvc_crepe_conv (the same kernel template, y bit-identical) that also writes code uint8 [N][Cout][Lc / 2]. With
+ *   z = conv + bias and v = relu(z) scale + shift at the position pair (2m, 2m + 1): the odd position wins only if v_odd > v_even (on a
+ *   tie the even one, as torch.max_pool2d's backward); code = 0 if the winner's z <= 0, else 1 (even winner) or 2 (odd winner).
+ * tdvc_crepe_conv_bwd: dy [N][Cout][Lc / 2], code, scale [Cout] -> dx [N][Cin][Lin] in one launch: dz[n][co][p] = dy[n][co][p >> 1]
+ *   scale[co] where code[n][co][p >> 1] == 1 + (p & 1), else 0 (a select: an unselected dy may hold anything); K 64, stride 1:
+ *   dx[n][ci][s] = sum_co sum_k w[co][ci][k] dz[n][co][s + 31 - k]; K 512, stride 4: dx[n][s] = sum_co sum_p w[co][s + 254 - 4 p]
+ *   dz[n][co][p] over 0 <= s + 254 - 4 p < 512; terms outside [0, Lc) are zero. An implicit GEMM on v_mfma_f32_16x16x4_f32, chunks
+ *   summed from zero and then accumulated. wt is the packed weight: K 64: wt[ci][co][k'] = w[co][ci][63 - k'] ([Cin][Cout 64]); K 512:
+ *   wt[r][co][i] = w[co][r + 510 - 4 i] where that tap exists, else 0 ([16][Cout 136]). wt and dx 16-byte aligned.
+ * tdvc_crepe_head_bwd: act [B][O][F] (N = B F frames, frame n = b F + f), w [O][P C] -> dx [N][C][P], dx[n][c][l] = sum_o dlogit[n][o]
+ *   w[o][l C + c] in float64, rounded once. Loss form (target and gL given, dact NULL): dlogit = gL[0] 2 (act - target) / (N O) act
+ *   (1 - act), target[b][o][f] at target[b t_bs + o t_cs + f t_fs], gL a DEVICE pointer to the upstream gradient. Plain form (dact dense
+ *   [B][O][F] given, target and gL NULL): dlogit = dact act (1 - act).
+ * tdvc_crepe_act_mse: out[0] = mean((act - target)^2) over [B][O][F], float64, a fixed order without atomics (written, not added).
+ * tdvc_crepe_frames_bwd: g [B][F][1024] (the gradient of the normalised frames) -> dsignal [B] rows of T (row stride d_bs). For a frame
+ *   with y = (x - mean) / den, den = max(1e-10, std): dxf = (g - mean(g) - y sum(g y) / 1023) / den if std > 1e-10, else (g - mean(g)) /
+ *   den; dsignal[b][q] = sum_f dxf[b][f][q - f hop + 512] over the frames that cover q, a gather in frame order, float64, one rounding.
+ *   Samples of the zero padding receive nothing. Rows are full length (no per-row lengths). Two launches; the workspace holds four
+ *   float64 per frame.
+ * tdvc_roll_bins: y[b][k][f] = x[b][(k - shift[b]) mod C][f] (util.roll_batches(x, shift, 1)); x at x[b x_bs + k x_cs + f], y dense, shift
+ *   device int64 [B].
+ * Every entry takes a stream; no atomics, fixed summation orders, no host synchronisation, graph-capturable. Refusals as the forward's
+ * (TDVC_EINVAL null pointers, negative sizes; TDVC_EUNSUPPORTED geometry other than the six layers', channel counts not multiples of
+ * 16, 2^31 elements of one operand or more, more than 512 head outputs; TDVC_EWORKSPACE), all before any launch. */
+typedef struct {
+  int32_t N, Cin, Cout, Lin, K, stride, reserved0, reserved1;
+  const float* dy;                            /* [N][Cout][Lc / 2] */
+  const uint8_t* code;                        /* [N][Cout][Lc / 2] */
+  const float* scale;                         /* [Cout] */
+  const float* wt;                            /* the packed weights, above */
+  float* dx;                                  /* [N][Cin][Lin] */
+} tdvc_crepe_conv_bwd_args;
+int tdvc_crepe_conv_train(const tdvc_crepe_conv_args* args, uint8_t* code, void* stream);
+int tdvc_crepe_conv_bwd(const tdvc_crepe_conv_bwd_args* args, void* stream);
+int tdvc_crepe_head_bwd(const float* act, const float* target, int64_t t_bs, int64_t t_cs, int64_t t_fs, const float* gL, const float* dact,
+                        const float* w, int32_t N, int32_t C, int32_t P, int32_t O, int32_t F, float* dx, void* stream);
+size_t tdvc_crepe_act_mse_workspace(void);
+int tdvc_crepe_act_mse(const float* act, const float* target, int64_t t_bs, int64_t t_cs, int64_t t_fs, int32_t B, int32_t O, int32_t F,
+                       float* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t tdvc_crepe_frames_bwd_workspace(int32_t B, int32_t F);
+int tdvc_crepe_frames_bwd(const float* signal, int64_t s_bs, int32_t T, int32_t B, int32_t hop, int32_t F, const float* g, float* dsignal,
+                          int64_t d_bs, void* workspace, size_t workspace_bytes, void* stream);
+int tdvc_roll_bins(const float* x, int64_t x_bs, int64_t x_cs, const int64_t* shift, float* y, int32_t B, int32_t C, int32_t F, void* stream);
 
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);

@@ -16,7 +16,9 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     load_ecapa / fbank / fbank_matrix / speaker_classify / running_mean_norm (ecapa.py), and the WavLM feature extractor that
     model/ssl_encoder.py injects into SSLEncoder (wavlm/WavLM.py extract_features) as WavLM / WavLMConfig / load_wavlm (wavlm.py), and
     the CREPE pitch tracker of util/crepe.py (torchcrepe's tiny / full network, its front end and its argmax, weighted-argmax and
-    Viterbi decoders) as Crepe / load_crepe / crepe_frames / crepe_decode / crepe_transition / get_shift (crepe.py).
+    Viterbi decoders) as Crepe / load_crepe / crepe_frames / crepe_decode / crepe_transition / get_shift (crepe.py), and the
+    activation-MSE F0 term of train.py:439-470 on it as losses.f0_crepe_loss / activation_mse / Crepe.activations_with_grad, with the
+    target of train.py:245-252 as conversion_target / roll_bins (StepConfig.f0_loss='activation').
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -49,7 +51,9 @@ def __getattr__(name):
         return getattr(importlib.import_module(f'{__name__}.ecapa'), name)
     if name in ('WavLM', 'WavLMConfig', 'load_wavlm'):
         return getattr(importlib.import_module(f'{__name__}.wavlm'), name)
-    if name in ('Crepe', 'load_crepe', 'crepe_frames', 'crepe_conv', 'crepe_head', 'crepe_decode', 'crepe_lattice', 'crepe_transition', 'get_shift'):
+    if name in ('Crepe', 'load_crepe', 'crepe_frames', 'crepe_conv', 'crepe_head', 'crepe_decode', 'crepe_lattice', 'crepe_transition', 'get_shift',
+                'crepe_conv_bwd', 'crepe_head_bwd', 'crepe_frames_bwd', 'crepe_act_mse', 'pack_bwd_weight', 'roll_bins', 'conversion_target',
+                'activation_mse'):
         return getattr(importlib.import_module(f'{__name__}.crepe'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)

@@ -92,6 +92,12 @@ class CrepeConvArgs(C.Structure):
                 ('scale', C.c_void_p), ('shift', C.c_void_p), ('y', C.c_void_p)]
 
 
+class CrepeConvBwdArgs(C.Structure):
+    _fields_ = [('N', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('Lin', C.c_int32), ('K', C.c_int32), ('stride', C.c_int32),
+                ('reserved0', C.c_int32), ('reserved1', C.c_int32), ('dy', C.c_void_p), ('code', C.c_void_p), ('scale', C.c_void_p),
+                ('wt', C.c_void_p), ('dx', C.c_void_p)]
+
+
 class L1Pair(C.Structure):
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('da', C.c_void_p), ('n', C.c_int64), ('weight', C.c_float)]
 
@@ -244,6 +250,14 @@ SIGNATURES = {
     'tdvc_crepe_head': (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     'tdvc_crepe_decode': (_i, [_vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp, _vp, _vp,
                                _vp]),
+    'tdvc_crepe_conv_train': (_i, [C.POINTER(CrepeConvArgs), _vp, _vp]),
+    'tdvc_crepe_conv_bwd': (_i, [C.POINTER(CrepeConvBwdArgs), _vp]),
+    'tdvc_crepe_head_bwd': (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    'tdvc_crepe_act_mse_workspace': (C.c_size_t, []),
+    'tdvc_crepe_act_mse': (_i, [_vp, _vp, _i64, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_size_t, _vp]),
+    'tdvc_crepe_frames_bwd_workspace': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'tdvc_crepe_frames_bwd': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
+    'tdvc_roll_bins': (_i, [_vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),

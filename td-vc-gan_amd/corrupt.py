@@ -106,13 +106,17 @@ def pair_targets(label_src, num_spk, conversion=True, perm=None, generator=None)
 
 @torch.no_grad()
 def device_batch(signal_real, label_src, num_spk, conversion=True, generator=None, sample_rate=16000, gains_db=None, z=None,
-                 perm=None, noise_src=None, noise_conv=None, start_phase_src=None, start_phase_conv=None):
+                 perm=None, noise_src=None, noise_conv=None, start_phase_src=None, start_phase_conv=None, f0_tracker=None):
     """The batch dict of train.py:214-256 from a device waveform batch signal_real [B, 1, T] and labels label_src [B] (int64):
     signal_corrupted = corrupt_audio(signal_real); the in-batch target pairing; F0 tracks from track_f0 (YIN), shifted towards the
     target speaker with infer.shift_f0 when converting; the two excitations from util.f0_to_excitation. Returns the keys TrainStep
     reads: signal_real, signal_corrupted, label_src, label_tgt, c_src, c_tgt, c_f0_src, c_f0_conv, f0_conv, perm.
     Every random draw is an optional input (gains_db, z [B, 10]; perm [B]; noise_* = (voiced, unvoiced) normal tensors [B, 1, T];
-    start_phase_* 1-element tensors), drawn on the device with `generator` otherwise. T must be a multiple of the F0 hop (64)."""
+    start_phase_* 1-element tensors), drawn on the device with `generator` otherwise. T must be a multiple of the F0 hop (64).
+    f0_tracker: a crepe.Crepe replaces YIN by the reference's own tracker (train.py:239, filtered_pitch with the argmax decoder), and
+    the dict gains f0_conv_activ [B, 360, T/64 + 1]: the target activations of TrainStep's f0_loss='activation', i.e. the source
+    activations rolled towards the target speaker (crepe.conversion_target, train.py:245-252), or the source activations themselves
+    with conversion=False (:242-243). With f0_tracker=None nothing changes."""
     H.need_device('device_batch', signal_real)
     if signal_real.dim() != 3 or signal_real.shape[1] != 1:
         raise ValueError('device_batch: signal_real must be [B, 1, T]')
@@ -124,8 +128,17 @@ def device_batch(signal_real, label_src, num_spk, conversion=True, generator=Non
     label_src = label_src.to(device=dev, dtype=torch.int64)
     perm, label_tgt, c_src, c_tgt = pair_targets(label_src, num_spk, conversion, perm, generator)
     corrupted = corrupt_audio(signal_real, sample_rate, gains_db=gains_db, z=z, generator=generator)
-    f0_src = track_f0(signal_real, hop=F0_HOP, sample_rate=sample_rate)
-    f0_conv = shift_f0(f0_src, f0_src[perm]) if conversion else f0_src
+    extra = {}
+    if f0_tracker is None:
+        f0_src = track_f0(signal_real, hop=F0_HOP, sample_rate=sample_rate)
+        f0_conv = shift_f0(f0_src, f0_src[perm]) if conversion else f0_src
+    else:
+        from .crepe import conversion_target
+        if sample_rate != 16000:
+            raise ValueError(f'device_batch: the CREPE tracker takes 16000 Hz audio, got {sample_rate}')
+        f0_src, act_src = f0_tracker.filtered_pitch(signal_real, 'argmax')
+        f0_conv, act_conv = conversion_target(f0_src, act_src, perm) if conversion else (f0_src, act_src)
+        extra['f0_conv_activ'] = act_conv
 
     def draws(noise, phase):
         if noise is None:
@@ -138,4 +151,4 @@ def device_batch(signal_real, label_src, num_spk, conversion=True, generator=Non
     c_f0_conv = f0_to_excitation(f0_conv, F0_HOP, sampling_rate=sample_rate, noise=n_c, start_phase=p_c)
     c_f0_src = f0_to_excitation(f0_src, F0_HOP, sampling_rate=sample_rate, noise=n_s, start_phase=p_s)
     return dict(signal_real=signal_real, signal_corrupted=corrupted, label_src=label_src, label_tgt=label_tgt, c_src=c_src, c_tgt=c_tgt,
-                c_f0_src=c_f0_src, c_f0_conv=c_f0_conv, f0_conv=f0_conv, perm=perm)
+                c_f0_src=c_f0_src, c_f0_conv=c_f0_conv, f0_conv=f0_conv, perm=perm, **extra)

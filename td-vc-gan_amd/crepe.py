@@ -36,11 +36,17 @@ Definition.
     frame, and `crepe_decode(lengths=frame counts)` gives pitch 0 and periodicity 0 there. The Viterbi decoder looks at the whole row,
     so it refuses per-row frame counts: decode such rows one at a time. The threshold comparison is made in fp32.
 
-Out of scope: the activation-MSE `lambda_f0` term of train.py:439-470 (a backward pass through this network, `roll_batches`),
-`TrainStep`, `bench.py` and `smoke()`: forward and inference only.
+The activation-MSE `lambda_f0` term of train.py:439-470 (g_loss_f0 = mse(activations(fake), target activations), :482) is
+`activation_mse` / `losses.f0_crepe_loss`, and `Crepe.activations_with_grad` is the differentiable forward: the network is fixed, so
+only d / d signal exists, and the backward keeps nothing of the forward but one byte per pooled output (which of the two positions
+won, and whether its ReLU was on: tdvc_crepe_conv_train) and the activations. Backward: tdvc_crepe_head_bwd (the loss gradient and
+the sigmoid fused), six tdvc_crepe_conv_bwd (unpool, mask, BatchNorm scale and the conv's input gradient in one launch each, from a
+transposed tap-flipped weight packing cached next to the folded BatchNorms), tdvc_crepe_frames_bwd. `roll_bins` and
+`conversion_target` build the target of train.py:245-252. Per-row `lengths` are refused on the differentiable path. The reference's
+dither is absent (above), so the target activations are the deterministic ones. Out of scope: `bench.py` and `smoke()`.
 
-Everything runs in csrc/pitch_crepe.hip (tdvc_crepe_frames, tdvc_crepe_conv, tdvc_crepe_head, tdvc_crepe_decode) and, for the Viterbi
-decoder, csrc/pitch_viterbi.hip: no CPU or ATen fallback, no host synchronisation, no atomics, fixed summation orders (bit-identical
+Everything runs in csrc/pitch_crepe.hip (tdvc_crepe_frames, tdvc_crepe_conv, tdvc_crepe_head, tdvc_crepe_decode), csrc/pitch_crepe_bwd.hip
+and, for the Viterbi decoder, csrc/pitch_viterbi.hip: no CPU or ATen fallback, no host synchronisation, no atomics, fixed summation orders (bit-identical
 from call to call, a row's result does not depend on its batch), every launch capturable into a graph.
 """
 import ctypes as C
@@ -166,10 +172,11 @@ def crepe_frames(signal, hop=HOP, lengths=None, sample_rate=SR):
     return frames
 
 
-def crepe_conv(x, weight, bias, scale, shift, stride=1, out=None):
+def crepe_conv(x, weight, bias, scale, shift, stride=1, out=None, train=False):
     """One conv block (tdvc_crepe_conv): x [N, Cin, Lin] dense fp32, weight [Cout, Cin, K(, 1)] -> maxpool2(relu(conv(x) + bias) scale +
     shift) fp32 [N, Cout, Lc / 2]; (Cin 1, K 512, stride 4, Lin 1024: Lc = 256) or (K 64, stride 1, Lin in 128, 64, 32, 16, 8: Lc =
-    Lin); Cout and (K 64) Cin multiples of 16."""
+    Lin); Cout and (K 64) Cin multiples of 16. train=True (tdvc_crepe_conv_train): -> (the same bits, code uint8 [N, Cout, Lc / 2]: 0 the
+    winner of the pooled pair has its ReLU off, 1 the even position won and is on, 2 the odd one)."""
     who = 'crepe_conv'
     H.need_device(who, x, weight)
     if x.dim() != 3 or weight.dim() not in (3, 4) or (weight.dim() == 4 and weight.shape[3] != 1):
@@ -190,6 +197,10 @@ def crepe_conv(x, weight, bias, scale, shift, stride=1, out=None):
     a = L.CrepeConvArgs()
     a.N, a.Cin, a.Cout, a.Lin, a.K, a.stride = N, Cin, Cout, Lin, K, int(stride)
     a.x, a.w, a.bias, a.scale, a.shift, a.y = x.data_ptr(), w.data_ptr(), bias.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr()
+    if train:
+        code = torch.empty(N, Cout, lout, dtype=torch.uint8, device=x.device)
+        H.check(who, L.lib().tdvc_crepe_conv_train(C.byref(a), code.data_ptr(), H.stream(x)))
+        return out, code
     H.check(who, L.lib().tdvc_crepe_conv(C.byref(a), H.stream(x)))
     return out
 
@@ -211,6 +222,232 @@ def crepe_head(x, weight, bias, frames_per_row=1):
     act = torch.empty((N // Fr, O, Fr) if Fr > 1 else (N, O), dtype=torch.float32, device=x.device)
     H.check(who, L.lib().tdvc_crepe_head(x.data_ptr(), N, Cc, P, w.data_ptr(), bias.data_ptr(), O, Fr, act.data_ptr(), H.stream(x)))
     return act
+
+
+# ------------------------------------------------------------------------------------------------------------------- backward
+L1_U = 136     # csrc/pitch_crepe.h CR_L1_U: the layer-1 backward reduces over 136 tap offsets per output channel, 132 of them live
+
+
+def pack_bwd_weight(weight):
+    """The weight of a conv block as tdvc_crepe_conv_bwd reads it (include/tdvc.h), fp32 contiguous on the weight's device: K 64:
+    wt[ci][co][k'] = w[co][ci][63 - k']; K 512 (Cin 1): wt[r][co][i] = w[co][r + 510 - 4 i] where that tap exists, else 0, r < 16, i < 136."""
+    w = weight.detach().float()
+    if w.dim() == 4 and w.shape[3] == 1:
+        w = w[..., 0]
+    if w.dim() != 3 or not ((w.shape[2] == 64) or (w.shape[2] == 512 and w.shape[1] == 1)):
+        raise ValueError(f'pack_bwd_weight: weight must be [Cout, Cin, 64(, 1)] or [Cout, 1, 512(, 1)], got {tuple(weight.shape)}')
+    if w.shape[2] == 64:
+        return w.flip(2).permute(1, 0, 2).contiguous()
+    tap = torch.arange(16, device=w.device)[:, None] + 510 - 4 * torch.arange(L1_U, device=w.device)[None, :]
+    live = (tap >= 0) & (tap < 512)
+    packed = w[:, 0, :][:, tap.clamp(0, 511)] * live                           # [Cout, 16, 136]
+    return packed.permute(1, 0, 2).contiguous()
+
+
+def crepe_conv_bwd(dy, code, scale, wt, Cin, Lin, K=64, stride=1, out=None):
+    """The backward of one conv block with respect to its input (tdvc_crepe_conv_bwd, one launch): dy fp32 and code uint8 [N, Cout, Lc / 2],
+    scale [Cout], wt = pack_bwd_weight(weight) -> dx fp32 [N, Cin, Lin]."""
+    who = 'crepe_conv_bwd'
+    H.need_device(who, dy, code, wt)
+    if dy.dim() != 3 or code.shape != dy.shape or code.dtype != torch.uint8:
+        raise ValueError(f'{who}: dy must be [N, Cout, Lc / 2] and code uint8 of that shape')
+    dy, code = dy.detach().float().contiguous(), code.contiguous()
+    N, Cout, lout = dy.shape
+    Cin, Lin, K, stride = int(Cin), int(Lin), int(K), int(stride)
+    if lout != (Lin // stride if stride else 0) // 2:
+        raise ValueError(f'{who}: {Lin} input positions at stride {stride} pool to {(Lin // stride if stride else 0) // 2} outputs, dy has {lout}')
+    scale = H.vec(who, scale, Cout, 'scale')
+    wt = H.vec(who, wt, (16 * Cout * L1_U) if K == 512 else Cin * Cout * K, 'the packed weight')
+    if out is None:
+        out = torch.empty(N, Cin, Lin, dtype=torch.float32, device=dy.device)
+    H.need_device(who, out)
+    if tuple(out.shape) != (N, Cin, Lin) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f'{who}: out must be contiguous fp32 [{N}, {Cin}, {Lin}]')
+    a = L.CrepeConvBwdArgs()
+    a.N, a.Cin, a.Cout, a.Lin, a.K, a.stride = N, Cin, Cout, Lin, K, stride
+    a.dy, a.code, a.scale, a.wt, a.dx = dy.data_ptr(), code.data_ptr(), scale.data_ptr(), wt.data_ptr(), out.data_ptr()
+    H.check(who, L.lib().tdvc_crepe_conv_bwd(C.byref(a), H.stream(dy)))
+    return out
+
+
+def _act3(who, act, weight, Cc, P):
+    H.need_device(who, act, weight)
+    if act.dim() == 2:
+        act = act[:, :, None]
+    if act.dim() != 3 or weight.dim() != 2 or weight.shape != (act.shape[1], P * Cc):
+        raise ValueError(f'{who}: act must be [B, O, F] (or [N, O]) and weight [O, {P * Cc}]')
+    return act.detach().float().contiguous()
+
+
+def _target_strides(who, act, target):
+    H.need_device(who, target)
+    if target.dim() == 2:
+        target = target[:, :, None]
+    if tuple(target.shape) != tuple(act.shape):
+        raise ValueError(f'{who}: the target must have the shape of the activations {tuple(act.shape)}, got {tuple(target.shape)}')
+    target = target.detach()
+    if target.dtype != torch.float32:
+        target = target.float()
+    return target, target.stride()
+
+
+def crepe_head_bwd(act, weight, Cc, P=4, target=None, gL=None, dact=None):
+    """The backward of the head (tdvc_crepe_head_bwd, one launch): act [B, O, F] from the forward, weight [O, P C] -> dx fp32 [B F, C, P].
+    Either the loss form, target [B, O, F] (any strides) and gL (a 1-element DEVICE tensor, the upstream gradient of mean((act -
+    target)^2); never read on the host), or the plain form dact [B, O, F]."""
+    who = 'crepe_head_bwd'
+    act = _act3(who, act, weight, Cc, P)
+    B, O, F = act.shape
+    w = H.vec(who, weight, O * P * Cc, 'weight')
+    if (dact is None) == (target is None) or (target is None) != (gL is None):
+        raise ValueError(f'{who}: takes either target and gL or dact')
+    ts = (0, 0, 0)
+    if dact is not None:
+        H.need_device(who, dact)
+        if dact.numel() != act.numel():
+            raise ValueError(f'{who}: dact must have the shape of the activations')
+        dact = dact.detach().float().contiguous()
+    else:
+        target, ts = _target_strides(who, act, target)
+        gL = H.vec(who, gL, 1, 'gL')
+    dx = torch.empty(B * F, Cc, P, dtype=torch.float32, device=act.device)
+    H.check(who, L.lib().tdvc_crepe_head_bwd(act.data_ptr(), H.ptr(target), ts[0], ts[1], ts[2], H.ptr(gL), H.ptr(dact), w.data_ptr(), B * F, Cc, P,
+                                             O, F, dx.data_ptr(), H.stream(act)))
+    return dx
+
+
+def crepe_act_mse(act, target):
+    """mean((act - target)^2) over act [B, O, F] as a 1-element fp32 tensor (tdvc_crepe_act_mse: float64 partial sums in a fixed order,
+    no atomics: the same bits eagerly and from a graph replay). target: any strides."""
+    who = 'crepe_act_mse'
+    H.need_device(who, act)
+    if act.dim() not in (2, 3):
+        raise ValueError(f'{who}: act must be [B, O, F] or [N, O]')
+    act = (act if act.dim() == 3 else act[:, :, None]).detach().float().contiguous()
+    target, ts = _target_strides(who, act, target)
+    B, O, F = act.shape
+    lib = L.lib()
+    nbytes = lib.tdvc_crepe_act_mse_workspace()
+    ws = H.scratch(nbytes, act.device)
+    out = torch.empty(1, dtype=torch.float32, device=act.device)
+    H.check(who, lib.tdvc_crepe_act_mse(act.data_ptr(), target.data_ptr(), ts[0], ts[1], ts[2], B, O, F, out.data_ptr(), ws.data_ptr(), nbytes,
+                                        H.stream(act)))
+    return out
+
+
+def crepe_frames_bwd(signal, g, hop=HOP):
+    """The backward of crepe_frames (tdvc_crepe_frames_bwd, two launches): signal [B, T] | [B, 1, T] | [T] as the forward took it (rows of
+    full length), g [B, F, 1024] the gradient of the normalised frames -> d signal, fp32 in the signal's shape."""
+    who = 'crepe_frames_bwd'
+    H.need_device(who, signal, g)
+    x2, bs, lead = H.rows2(who, signal)
+    B, T = x2.shape
+    hop = int(hop)
+    if hop < 1 or T < 1:
+        raise ValueError(f'{who}: hop must be at least 1 and rows need a sample')
+    F = num_frames(T, hop)
+    if g.numel() != B * F * WINDOW:
+        raise ValueError(f'{who}: g must be [{B}, {F}, {WINDOW}], got {tuple(g.shape)}')
+    g = g.detach().float().contiguous()
+    lib = L.lib()
+    nbytes = lib.tdvc_crepe_frames_bwd_workspace(B, F)
+    ws = H.scratch(nbytes, x2.device)
+    dx = torch.empty(B, T, dtype=torch.float32, device=x2.device)
+    H.check(who, lib.tdvc_crepe_frames_bwd(x2.data_ptr(), bs, T, B, hop, F, g.data_ptr(), dx.data_ptr(), T, ws.data_ptr(), nbytes, H.stream(x2)))
+    return dx.reshape(lead + (T,))
+
+
+def roll_bins(act, shift):
+    """util.roll_batches(act, shift, 1) of the reference (util/__init__.py:91-102) on act [B, C, F] (device fp32, any strides): row b is
+    rolled along the bin axis by shift[b] (integers, any shape of B elements, either sign): out[b, k] = act[b, (k - shift[b]) mod C]
+    (tdvc_roll_bins, one launch)."""
+    who = 'roll_bins'
+    H.need_device(who, act)
+    if act.dim() != 3:
+        raise ValueError(f'{who}: act must be [B, C, F], got {tuple(act.shape)}')
+    act = act.detach().float()
+    B, Cb, F = act.shape
+    if F > 1 and act.stride(2) != 1:
+        act = act.contiguous()
+    shift = torch.as_tensor(shift, device=act.device)
+    if shift.is_floating_point() or shift.numel() != B:
+        raise ValueError(f'{who}: shift must hold {B} integers')
+    shift = shift.reshape(-1).to(torch.int64).contiguous()
+    out = torch.empty(B, Cb, F, dtype=torch.float32, device=act.device)
+    H.check(who, L.lib().tdvc_roll_bins(act.data_ptr(), act.stride(0), act.stride(1), shift.data_ptr(), out.data_ptr(), B, Cb, F, H.stream(act)))
+    return out
+
+
+def conversion_target(f0_src, act_src, perm):
+    """train.py:245-252: the F0 track and the target activations of a conversion towards the speakers f0_src[perm]. f0_src [B, 1, F] or
+    [B, F] in Hz (0 = unvoiced), act_src [B, 360, F], perm [B] -> (f0_conv_tgt, act_tgt): the log-F0 mean shift of `infer.shift_f0`
+    (mu = sum(voiced log(f0 + 1e-6)) / (voiced frames + 1e-6); a row without a voiced frame has mu = 0, i.e. a mean of 1 Hz, as in the
+    reference) and the source activations rolled along the bins by get_shift(exp(mu_src), exp(mu_tgt))."""
+    from .infer import shift_f0
+    f0_tgt = f0_src[perm]
+
+    def mu(f):
+        v = f > 0
+        return torch.sum(v * torch.log(f + 1e-6), -1, keepdim=True) / (torch.sum(v, -1, keepdim=True) + 1e-6)
+    shift = get_shift(torch.exp(mu(f0_src)), torch.exp(mu(f0_tgt)))
+    return shift_f0(f0_src, f0_tgt), roll_bins(act_src, shift)
+
+
+class _ActivationsFn(torch.autograd.Function):
+    """Crepe.activations_with_grad. Saved for the backward: the signal, the activations and one byte per pooled output."""
+
+    @staticmethod
+    def forward(ctx, x2, model, hop, target):
+        act, codes = model._forward_train(x2, hop)
+        ctx.model, ctx.hop, ctx.with_loss = model, hop, target is not None
+        if target is None:
+            ctx.save_for_backward(x2, act, *codes)
+            return act
+        ctx.save_for_backward(x2, act, target, *codes)
+        ctx.mark_non_differentiable(act)
+        return crepe_act_mse(act, target), act
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        m = ctx.model
+        x2, act = ctx.saved_tensors[:2]
+        c6 = CAPACITIES[m.capacity][-1]
+        if ctx.with_loss:      # the loss gradient, the sigmoid and the classifier in one launch; g stays on the device
+            target, codes = ctx.saved_tensors[2], ctx.saved_tensors[3:]
+            dx = crepe_head_bwd(act, m.classifier.weight, c6, 4, target=target, gL=g)
+        else:
+            codes = ctx.saved_tensors[2:]
+            dx = crepe_head_bwd(act, m.classifier.weight, c6, 4, dact=g)
+        gfr = m._backward_blocks(dx, codes)
+        return crepe_frames_bwd(x2, gfr, ctx.hop), None, None, None
+
+
+def _grad_rows(who, signal, model, hop, lengths, sample_rate):
+    _check_rate(who, sample_rate)
+    if lengths is not None:
+        raise ValueError(f'{who}: per-row lengths are not part of the differentiable path (rows are full length)')
+    H.need_device(who, signal, model.classifier.weight)
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f'{who}: hop must be at least 1, got {hop}')
+    x2, _, _ = H.rows2(who, signal, keep_grad=True)
+    if x2.shape[1] < 1:
+        raise ValueError(f'{who}: rows with no sample are refused')
+    return x2, hop
+
+
+def activation_mse(signal, target_activ, model, hop=HOP, sample_rate=SR):
+    """The reference's F0 term (train.py:439-470): mean((model.activations(signal) - target_activ)^2) as a 1-element tensor that is
+    differentiable in signal [B, 1, T] | [B, T] | [T]; target_activ [B, 360, F] (a view is fine) gets no gradient. -> (loss,
+    activations). The value comes from tdvc_crepe_act_mse; the backward is tdvc_crepe_head_bwd with the loss gradient fused, six
+    tdvc_crepe_conv_bwd and tdvc_crepe_frames_bwd."""
+    who = 'activation_mse'
+    x2, hop = _grad_rows(who, signal, model, hop, None, sample_rate)
+    H.need_device(who, target_activ)
+    want = (x2.shape[0], BINS, num_frames(x2.shape[1], hop))
+    if tuple(target_activ.shape) != want:
+        raise ValueError(f'{who}: target_activ must be {list(want)} for this signal, got {list(target_activ.shape)}')
+    return _ActivationsFn.apply(x2, model, hop, target_activ.detach().float())
 
 
 def _decode_call(who, act, lo, hi, mode, threshold, frames=None, bins=None):
@@ -293,16 +530,52 @@ class Crepe(torch.nn.Module):
         self.in_features = 4 * out[-1]
         self.classifier = torch.nn.Linear(self.in_features, BINS)
         self._folded = {}
+        self._packed = {}
         self.eval()
 
     def load_state_dict(self, *args, **kwargs):
         out = super().load_state_dict(*args, **kwargs)
-        self._folded = {}
+        self._folded, self._packed = {}, {}
         return out
 
     def _apply(self, fn, *args, **kwargs):
-        self._folded = {}
+        self._folded, self._packed = {}, {}
         return super()._apply(fn, *args, **kwargs)
+
+    def _pack(self, device):
+        """The six weights as the backward reads them (pack_bwd_weight), once per device like the folded BatchNorms."""
+        k = H.dev_key(device)
+        if k not in self._packed:
+            self._packed[k] = [pack_bwd_weight(getattr(self, f'conv{i}').weight) for i in range(1, 7)]
+        return self._packed[k]
+
+    def _forward_train(self, x2, hop):
+        """x2 [B, T] -> (activations [B, 360, F], the six code tensors): `activations` with tdvc_crepe_conv_train."""
+        frames = crepe_frames(x2, hop)
+        B, F, _ = frames.shape
+        fold = self._fold(frames.device)
+        x, codes = frames.view(B * F, 1, WINDOW), []
+        for i in range(1, 7):
+            conv = getattr(self, f'conv{i}')
+            x, code = crepe_conv(x, conv.weight, conv.bias, *fold[i - 1], stride=conv.stride[0], train=True)
+            codes.append(code)
+        return crepe_head(x, self.classifier.weight, self.classifier.bias, frames_per_row=F).view(B, BINS, F), codes
+
+    def _backward_blocks(self, dx, codes):
+        """dx [N, C6, 4] (the gradient of the last block's output) -> the gradient of the normalised frames [N, 1, 1024]: six
+        tdvc_crepe_conv_bwd launches."""
+        fold, packed = self._fold(dx.device), self._pack(dx.device)
+        for i in range(6, 0, -1):
+            conv = getattr(self, f'conv{i}')
+            dx = crepe_conv_bwd(dx, codes[i - 1], fold[i - 1][0], packed[i - 1], conv.in_channels, WINDOW if i == 1 else 256 >> (i - 1),
+                                conv.kernel_size[0], conv.stride[0])
+        return dx
+
+    def activations_with_grad(self, signal, hop=HOP, lengths=None, sample_rate=SR):
+        """`activations` (the same bits) as a tensor that is differentiable in signal; the weights are fixed and get no gradient.
+        Only the codes of tdvc_crepe_conv_train and the activations are kept for the backward. lengths: refused."""
+        x2, hop = _grad_rows('Crepe.activations_with_grad', signal, self, hop, lengths, sample_rate)
+        return _ActivationsFn.apply(x2, self, hop, None)
 
     def _fold(self, device):
         k = H.dev_key(device)

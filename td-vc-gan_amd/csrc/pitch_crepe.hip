@@ -1,5 +1,7 @@
 // The CREPE pitch tracker (torchcrepe's `tiny` and `full` networks, the reference's util/crepe.py filtered_pitch), restated in
-// include/tdvc.h: the framing front end, the six conv blocks, the classifier head and the per-frame decoders. Forward only.
+// include/tdvc.h: the framing front end, the six conv blocks, the classifier head and the per-frame decoders. The forward; the backward
+// with respect to the signal is pitch_crepe_bwd.hip, which needs tdvc_crepe_conv_train here: the conv launch that also writes the pooling
+// decision of every output (one kernel template, a compile-time switch, the same instructions for y).
 //
 // tdvc_crepe_frames  a block per frame: 1024 samples around f hop (the row zero-padded by 512 on both sides, samples at and past the
 //                    row's length never read), mean and unbiased standard deviation in float64 (two passes, pairwise combine of the
@@ -31,17 +33,13 @@
 
 #include "../../include/tdvc.h"
 #include "api_util.h"
+#include "pitch_crepe.h"
 #include "reduce.h"
 
 namespace tdvc {
 
-constexpr int CR_WIN = 1024, CR_BINS = 360, CR_THREADS = 256;
-constexpr int CR_KCH = 128;          // products per chunk and chain
-constexpr int CR_WP = 130;           // ws row pitch
 constexpr int CR_PL = 304;           // phase plane pitch of the stride-4 geometry: 256 + 32 words used
 constexpr double CR_CENTS0 = 1997.3794084376191;
-
-typedef float cr_f32x4 __attribute__((ext_vector_type(4)));
 
 // ----------------------------------------------------------------------------------------------------------------- frames
 __global__ __launch_bounds__(256) void crepe_frames_kernel(const float* x, long x_bs, const int* lengths, int T, int hop, int F, float* out) {
@@ -79,10 +77,12 @@ struct CrConvP {
   int N, Cin, Cout;
   const float* x; const float* w; const float* bias; const float* scale; const float* shift;
   float* y;
+  unsigned char* code;                                           // TRAIN only: [N][Cout][LC / 2]
 };
 
 // S = 4: Cin = 1, K = 512, 1024 samples in, LC = 256 conv positions. S = 1: K = 64, LC positions in and out.
-template <int S, int LC>
+// TRAIN: also the pooling decision of every output (tdvc_crepe_conv_train); y is computed by the same instructions either way.
+template <int S, int LC, bool TRAIN>
 __global__ __launch_bounds__(CR_THREADS, 2) void crepe_conv_kernel(CrConvP p) {
   constexpr int FPB = 256 / LC;                                  // frames per block
   constexpr int CH = S == 4 ? 1 : 2;                             // input channels per chunk
@@ -186,9 +186,18 @@ __global__ __launch_bounds__(CR_THREADS, 2) void crepe_conv_kernel(CrConvP p) {
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       const int col = 64 * wv + 16 * nt + j, n = n0 + col / LC, pos = col % LC;
-      const float v = fmaf(fmaxf(acc[nt][r] + bi, 0.f), sc, sh);
-      const float m = fmaxf(v, __shfl_xor(v, 1));                           // the other position of the pair: the neighbouring lane
-      if (!(j & 1) && n < p.N) p.y[((long)n * p.Cout + co) * LOUT + (pos >> 1)] = m;
+      const float z = acc[nt][r] + bi;
+      const float v = fmaf(fmaxf(z, 0.f), sc, sh);
+      const float vo = __shfl_xor(v, 1);                                    // the other position of the pair: the neighbouring lane
+      const float m = fmaxf(v, vo);
+      const long at = ((long)n * p.Cout + co) * LOUT + (pos >> 1);
+      if constexpr (TRAIN) {                                                // the odd position wins only if it is strictly larger
+        const float zo = __shfl_xor(z, 1);
+        const bool odd = vo > v;
+        const unsigned char cd = (odd ? zo : z) <= 0.f ? CR_CODE_DEAD : (odd ? CR_CODE_ODD : CR_CODE_EVEN);
+        if (!(j & 1) && n < p.N) p.code[at] = cd;
+      }
+      if (!(j & 1) && n < p.N) p.y[at] = m;
     }
   }
 }
@@ -275,8 +284,13 @@ __global__ __launch_bounds__(64) void crepe_decode_kernel(CrDecP p) {
 template <int S, int LC>
 static void crepe_conv_launch(const CrConvP& p, hipStream_t st) {
   constexpr int FPB = 256 / LC;
-  hipLaunchKernelGGL((crepe_conv_kernel<S, LC>), dim3((p.N + FPB - 1) / FPB, p.Cout / 16), dim3(CR_THREADS), 0, st, p);
+  const dim3 grid((p.N + FPB - 1) / FPB, p.Cout / 16);
+  if (p.code) hipLaunchKernelGGL((crepe_conv_kernel<S, LC, true>), grid, dim3(CR_THREADS), 0, st, p);
+  else hipLaunchKernelGGL((crepe_conv_kernel<S, LC, false>), grid, dim3(CR_THREADS), 0, st, p);
 }
+
+// the checks and the launch of tdvc_crepe_conv and tdvc_crepe_conv_train: code == nullptr is the plain forward
+static int crepe_conv_run(const tdvc_crepe_conv_args* a, unsigned char* code, bool train, void* stream);
 
 }  // namespace tdvc
 
@@ -295,8 +309,11 @@ extern "C" int tdvc_crepe_frames(const float* signal, int64_t s_bs, const int32_
   return TDVC_OK;
 }
 
-extern "C" int tdvc_crepe_conv(const tdvc_crepe_conv_args* a, void* stream) {
-  using namespace tdvc;
+extern "C" int tdvc_crepe_conv(const tdvc_crepe_conv_args* a, void* stream) { return tdvc::crepe_conv_run(a, nullptr, false, stream); }
+
+extern "C" int tdvc_crepe_conv_train(const tdvc_crepe_conv_args* a, uint8_t* code, void* stream) { return tdvc::crepe_conv_run(a, code, true, stream); }
+
+static int tdvc::crepe_conv_run(const tdvc_crepe_conv_args* a, unsigned char* code, bool train, void* stream) {
   if (!a) return tdvc_fail(TDVC_EINVAL, "crepe_conv: null arguments");
   if (a->N < 0 || a->Cin < 1 || a->Cout < 1) return tdvc_fail(TDVC_EINVAL, "crepe_conv: negative N or a channel count below 1");
   const bool first = a->stride == 4 && a->K == 512 && a->Cin == 1 && a->Lin == CR_WIN;
@@ -308,10 +325,10 @@ extern "C" int tdvc_crepe_conv(const tdvc_crepe_conv_args* a, void* stream) {
   if (a->Cout > (1 << 16) || (double)a->N * a->Cin * a->Lin > 2147483647.0 || (double)a->N * a->Cout * (lc / 2) > 2147483647.0 || a->N > (1 << 22))
     return tdvc_fail(TDVC_EUNSUPPORTED, "crepe_conv: more than 2^16 output channels, 2^22 frames or 2^31 elements");
   if (a->N == 0) return TDVC_OK;
-  if (!a->x || !a->w || !a->bias || !a->scale || !a->shift || !a->y) return tdvc_fail(TDVC_EINVAL, "crepe_conv: null pointer");
+  if (!a->x || !a->w || !a->bias || !a->scale || !a->shift || !a->y || (train && !code)) return tdvc_fail(TDVC_EINVAL, "crepe_conv: null pointer");
   if (((uintptr_t)a->w & 15) != 0) return tdvc_fail(TDVC_EINVAL, "crepe_conv: weights must be 16-byte aligned");
   CrConvP p;
-  p.N = a->N; p.Cin = a->Cin; p.Cout = a->Cout; p.x = a->x; p.w = a->w; p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.y = a->y;
+  p.N = a->N; p.Cin = a->Cin; p.Cout = a->Cout; p.x = a->x; p.w = a->w; p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.y = a->y; p.code = code;
   hipStream_t st = (hipStream_t)stream;
   if (first) crepe_conv_launch<4, 256>(p, st);
   else if (lc == 128) crepe_conv_launch<1, 128>(p, st);

@@ -443,6 +443,24 @@ def f0_yin_loss(signal, f0_tgt, hop=64, sample_rate=16000, pitch_min=60, pitch_m
     return ((v * e * e).sum() / v.sum().clamp(min=1.0)).reshape(1)
 
 
+# ------------------------------------------------------------------------------- F0 (CREPE activations)
+def f0_crepe_loss(signal, target_activ, model, hop=64, sample_rate=16000):
+    """The reference's live F0 term (train.py:439-470, :482): F.mse_loss(filtered_pitch(signal)[1], target_activ.detach()) on the CREPE
+    activations of the device tracker `model` (crepe.Crepe): signal [B, 1, T], target_activ [B, 360, T // hop + 1] (a view is fine, no
+    gradient) -> 1-element tensor, differentiable in signal. The network's weights are fixed. Forward: tdvc_crepe_frames, six
+    tdvc_crepe_conv_train, tdvc_crepe_head, tdvc_crepe_act_mse; backward: tdvc_crepe_head_bwd (with the loss gradient, read from the
+    device), six tdvc_crepe_conv_bwd, tdvc_crepe_frames_bwd (csrc/pitch_crepe_bwd.hip). No host synchronisation, no atomics: the value
+    and the gradient have the same bits from call to call and from a graph replay."""
+    from . import crepe as CR
+    from ._host import need_device
+    need_device('f0_crepe_loss', signal, target_activ)
+    if not isinstance(model, CR.Crepe):
+        raise ValueError('f0_crepe_loss: model must be a crepe.Crepe')
+    if signal.dim() != 3 or signal.shape[1] != 1:
+        raise ValueError('f0_crepe_loss: signal must be [B, 1, T]')
+    return CR.activation_mse(signal, target_activ, model, hop=hop, sample_rate=sample_rate)[0]
+
+
 # ------------------------------------------------------------------------------- contrastive
 class _ContrastiveFn(Function):
     @staticmethod

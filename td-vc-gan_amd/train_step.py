@@ -3,8 +3,9 @@
 Mirrors the loop body of the reference's train.py:209-521 (D-step :259-316, G-step :320-510,
 loss assembly :477-482, optimizers :188-189; cycle-reconstruction branch :344-361 when lambda_rec > 0)
 for the configuration space of the shipped YAMLs,
-minus the CREPE-backed F0 term (:429-470, torchcrepe unavailable: SURVEY §8c; the reference's commented YIN route to the same
-term, :438/:441/:466-467, is available as the opt-in `f0_loss='yin'`) and minus work
+with the CREPE-backed F0 term (:429-470) behind `f0_loss='activation'` (losses.f0_crepe_loss on the device tracker crepe.Crepe,
+handed in as `f0_model`; torchcrepe itself and its weights are not shipped: SURVEY §8c; the reference's commented YIN route to the same
+term, :438/:441/:466-467, is the opt-in `f0_loss='yin'`; by default lambda_f0 reaches no loss) and minus work
 that reaches no parameter update:
   Q3  the D-step's generator forward runs without a graph (the reference back-propagates into G
       through the sub-scale heads and then discards those gradients);
@@ -20,6 +21,9 @@ import torch
 
 from . import losses as LS
 from .arena import FlatAdamW
+
+
+F0_LOSSES = (None, 'yin', 'activation')
 
 
 @dataclass
@@ -49,21 +53,25 @@ class StepConfig:
     d_step_interval: int = 1            # train.py:259
     g_step_interval: int = 1            # train.py:320
     freeze_subnets: tuple = ()          # train.py:195-197: ('encoder',) -> G.encoder parameters get requires_grad = False
-    f0_loss: str = None                 # None: lambda_f0 reaches no loss; 'yin': lambda_f0 * losses.f0_yin_loss(fake, batch['f0_conv'])
+    f0_loss: str = None                 # None: lambda_f0 reaches no loss; 'yin': lambda_f0 * losses.f0_yin_loss(fake, batch['f0_conv']);
+                                        # 'activation': lambda_f0 * losses.f0_crepe_loss(fake, batch['f0_conv_activ'], f0_model)
 
     @staticmethod
     def from_hparams(train: dict, f0_loss: str = None) -> 'StepConfig':
         """Build from the `train` document of a reference YAML (config/*.yaml). `lambda_f0` (the CREPE-backed F0 term,
-        train.py:429-470) is excluded by contract (torchcrepe is not available: SURVEY §8c) and only warns, unless the caller
-        opts into the soft-YIN route with f0_loss='yin' (losses.f0_yin_loss; the step then needs batch['f0_conv']); a sub-network
+        train.py:429-470) is off by default (torchcrepe's weights are not shipped: SURVEY §8c) and only warns, unless the caller
+        opts into the soft-YIN route with f0_loss='yin' (losses.f0_yin_loss; the step then needs batch['f0_conv']) or into the
+        reference's own activation term with f0_loss='activation' (losses.f0_crepe_loss; the step then needs a crepe.Crepe as
+        TrainStep(f0_model=) and batch['f0_conv_activ']); a sub-network
         name in `freeze_subnets` other than 'encoder' is ignored by the reference too (train.py:195)."""
         g = train.get
-        if f0_loss not in (None, 'yin'):
-            raise ValueError(f"f0_loss must be None or 'yin', got {f0_loss!r}")
+        if f0_loss not in F0_LOSSES:
+            raise ValueError(f"f0_loss must be None, 'yin' or 'activation', got {f0_loss!r}")
         if f0_loss is None and float(g('lambda_f0', 0) or 0) != 0:
             import warnings
-            warnings.warn('lambda_f0 != 0: the CREPE-backed F0 loss term (train.py:429-470) is not part of this path '
-                          '(torchcrepe unavailable); the iteration runs without it', stacklevel=2)
+            warnings.warn("lambda_f0 != 0: the CREPE-backed F0 loss term (train.py:429-470) is off unless asked for with f0_loss='activation' "
+                          "(and a crepe.Crepe holding the tracker's weights, which are not shipped) or f0_loss='yin'; the iteration runs "
+                          "without it", stacklevel=2)
         return StepConfig(no_conv=bool(g('no_conv', False)), lambda_rec=float(g('lambda_rec', 0)),
                           lambda_idt=float(g('lambda_idt', 0)), lambda_feat=float(g('lambda_feat', 0)),
                           lambda_spec=float(g('lambda_spec', 0)), lambda_cont_emb=float(g('lambda_cont_emb', 0)),
@@ -80,14 +88,17 @@ class StepConfig:
 
 
 class TrainStep:
-    def __init__(self, G, D, cfg: StepConfig, device, reuse_fake=True, grad_sync=None, C=None):
+    def __init__(self, G, D, cfg: StepConfig, device, reuse_fake=True, grad_sync=None, C=None, f0_model=None):
         self.G, self.D, self.cfg, self.device = G, D, cfg, torch.device(device)
         self.reuse_fake = reuse_fake
         self.grad_sync = grad_sync            # parallel.GradSync or None
         self.comm_events = None               # set to [] to record (backward done, all-reduce joined) event pairs per optimizer step
         self.iter_count = 0                   # train.py:211: the step intervals count iterations from 0
-        if cfg.f0_loss not in (None, 'yin'):
-            raise ValueError(f"StepConfig.f0_loss must be None or 'yin', got {cfg.f0_loss!r}")
+        if cfg.f0_loss not in F0_LOSSES:
+            raise ValueError(f"StepConfig.f0_loss must be None, 'yin' or 'activation', got {cfg.f0_loss!r}")
+        if cfg.f0_loss == 'activation' and f0_model is None:
+            raise ValueError("f0_loss='activation' needs the pitch tracker: TrainStep(..., f0_model=crepe.Crepe)")
+        self.f0_model = f0_model              # crepe.Crepe, fixed weights (train.py:439: util.crepe.filtered_pitch(signal_fake))
         if 'encoder' in cfg.freeze_subnets:   # train.py:195-197
             for p_ in G.encoder.parameters():
                 p_.requires_grad = False
@@ -190,6 +201,10 @@ class TrainStep:
         real = batch['signal_real']
         B = real.shape[0]
         want_f0 = c.f0_loss == 'yin' and c.lambda_f0 != 0
+        want_f0_activ = c.f0_loss == 'activation' and c.lambda_f0 != 0
+        if want_f0_activ and 'f0_conv_activ' not in batch:
+            raise ValueError("f0_loss='activation' with lambda_f0 != 0 needs batch['f0_conv_activ']: the [B, 360, T/64 + 1] target "
+                             "activations (crepe.conversion_target, or the source activations with no_conv)")
         if want_f0 and 'f0_conv' not in batch:
             raise ValueError("f0_loss='yin' with lambda_f0 != 0 needs batch['f0_conv']: the [B, 1, T/64 + 1] F0 track in Hz that the "
                              "excitation batch['c_f0_conv'] was made from")
@@ -314,6 +329,10 @@ class TrainStep:
                 total = total + c.lambda_latcls * l_cls
             if want_f0:                 # train.py:438, :441, :466-467 (the YIN route), tag as in train.py:501
                 l_f0 = LS.f0_yin_loss(fake, batch['f0_conv'])
+                log['g_loss_f0'] = l_f0.detach()
+                total = total + c.lambda_f0 * l_f0
+            if want_f0_activ:           # train.py:439-470, :482: the activation MSE through the fixed tracker, tag as in train.py:501
+                l_f0 = LS.f0_crepe_loss(fake, batch['f0_conv_activ'], self.f0_model)
                 log['g_loss_f0'] = l_f0.detach()
                 total = total + c.lambda_f0 * l_f0
             if emb_cor is not None:
