@@ -55,6 +55,20 @@ constexpr int lean_min_blocks(int m_rep, int n_rep, int wm, int xfk) {
   if (m_rep == 1 && n_rep == 4 && wm == 1 && xfk == LXF_ACT) return 5;   // 16 x 256 tile, plain prologue: 5 resident blocks (<= 96 VGPRs) is what the HBM-bound convs run at
   return m_rep * n_rep >= 9 ? 2 : ((m_rep * n_rep >= 8 || (wm == 4 && xfk == LXF_FILM)) ? 3 : LEAN_OCC_SMALL);   // (FiLM prologue on 64 x 64: 12 spills at 4)
 }
+#ifndef LEAN_RING_1
+#define LEAN_RING_1 2         // fragment sets in flight on the tiles with one MFMA per step (A/B knob: make ab EXTRA=-DLEAN_RING_1=4)
+#endif
+#ifndef LEAN_RING_2
+#define LEAN_RING_2 2         // ... with two MFMAs per step
+#endif
+// Depth of the fragment ring of the MFMA loop; 0 = the one-step-ahead loop with its scalar (tap, channel-group) walk. A wave with one
+// or two accumulators has 32 / 64 cycles of matrix work per step and one to four such waves share a SIMD: what a step costs there
+// is the instructions it issues around the MFMA (the scalar walk with its branches: 165-360 cycles per step measured), more than the
+// LDS latency the loop waits for. The ring loop walks one tap at a time, so a step is the reads, two address adds and the MFMAs,
+// with the reads issued `depth` steps ahead of their use and each use waiting for its own reads only (counted lgkmcnt). Measured
+// on the classes of profiles/r06_a_lean_frag_pipe_ab.txt, depth 2 beats 4 and 8 on both tiles (deeper rings pay more for the
+// fill and drain of every tap than they hide). From four MFMAs per step on the one-step-ahead loop stays.
+constexpr int lean_ring_depth(int m_rep, int n_rep) { return m_rep * n_rep == 1 ? LEAN_RING_1 : (m_rep * n_rep == 2 ? LEAN_RING_2 : 0); }
 // FOLD: short sequences (T = 16 / 32: discriminator layer 5 of the two sub-sampled discriminators) put p.fold = 64 / T SAMPLES
 // side by side in one 64-column tile -- segment s of the LDS tile holds sample b0 + s with its own zero-padded halo, sub-tile
 // n of the MFMA loop reads from its sample's segment, the epilogue scatters the sub-tiles back to their samples. Without it
@@ -126,7 +140,10 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
     const int sg = vv / nvs, q = q0 + 4 * (vv - sg * nvs);
     xw.voff = (xw.active && q >= 0 && q < p.T && b + sg < p.Bn) ? (sg * p.x_bs + rsub * p.T + q) * 4 : 0x7f000000;
   }
-  const int fold_bytes = FOLD ? (p.fold - 1) * p.x_bs * 4 : 0;      // the descriptors span the tile's samples
+  // The descriptors span the tile's samples -- the ones that exist: the row walk's passes run past the chunk's rows and count on the
+  // descriptor's end to turn those loads into zeros, so a range reaching over absent samples of the last group let the rows behind
+  // the last sample's channels be read from behind the tensor.
+  const int fold_bytes = FOLD ? (min(p.fold, p.Bn - b) - 1) * p.x_bs * 4 : 0;
   const RowWalk ww = make_walk(tid, jc >> 2, p.wrp, p.Cw, p.WS, 0, 1 << 30);
   RegTile<XVP> xr;
   RegTile<WVP> wr;
@@ -316,7 +333,9 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
       if (++scs == csteps) { scs = 0; ++sj; woff = p.flip ? p.K - 1 - sj : sj; xoff = sj * p.d; }
       else { woff += 4 * p.K; xoff += 4 * p.XS; }
     };
-    float wv[2][M_REP], xv[2][N_REP];
+    constexpr int DEPTH = lean_ring_depth(M_REP, N_REP);
+    constexpr int NSET = DEPTH > 2 ? DEPTH : 2;
+    float wv[NSET][M_REP], xv[NSET][N_REP];
     int noff[N_REP];                                       // LDS column of sub-tile n relative to the wave's first column
 #pragma unroll
     for (int n = 0; n < N_REP; ++n) {
@@ -338,15 +357,60 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
         for (int n = 0; n < N_REP; ++n)
           acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[buf][n], wv[buf][m], acc[m][n], 0, 0, 0);
     };
-    load_frag(0);
-    int s = 0;
-    for (; s + 2 <= nsteps; s += 2) {
-      advance(); load_frag(1);
-      mma(0);
-      if (s + 2 < nsteps) { advance(); load_frag(0); }
-      mma(1);
+    // Fragment ring (tiles with one or two MFMAs per step), run once per tap over its n channel groups: a slot is one step's
+    // fragments. The n % DEPTH odd steps run first: their reads go out together, then their MFMAs. The other steps run in rounds of
+    // DEPTH: the reads of the first round go out up front, each later round runs the MFMAs of slot i and refills it with the step
+    // DEPTH ahead, the last round only drains. Each stage is straight-line code with fixed slot registers, so the wait in front of
+    // an MFMA counts the younger reads still in flight (a wait the compiler places behind a branch merge is lgkmcnt(0)). No read
+    // is issued for a step >= n. issue() reads at its cursor and advances it; use() takes the slots in order.
+    auto ring_run = [&](const int n, auto&& issue, auto&& use) {
+      const int rounds = n / DEPTH, odd = n - rounds * DEPTH;
+#pragma unroll
+      for (int i = 0; i < DEPTH - 1; ++i)
+        if (i < odd) issue(i);
+#pragma unroll
+      for (int i = 0; i < DEPTH - 1; ++i)
+        if (i < odd) use(i);
+      if (rounds > 0) {
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) issue(i);
+        for (int r = 1; r < rounds; ++r) {
+#pragma unroll
+          for (int i = 0; i < DEPTH; ++i) {
+            use(i); issue(i);
+            __builtin_amdgcn_sched_barrier(0);             // keep the steps apart: grouped, the reads of a whole round wait behind one lgkmcnt(0)
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) use(i);
+      }
+    };
+    auto one_ahead_run = [&]() {
+      load_frag(0);
+      int s = 0;
+      for (; s + 2 <= nsteps; s += 2) {
+        advance(); load_frag(1);
+        mma(0);
+        if (s + 2 < nsteps) { advance(); load_frag(0); }
+        mma(1);
+      }
+      if (s < nsteps) mma(0);
+    };
+    if constexpr (DEPTH == 0) one_ahead_run();
+    else if (p.one_ahead) one_ahead_run();                 // test-only (tdvc_debug_knob 8): the ring's results are compared with this loop's
+    else {
+      for (int j = 0; j < p.K; ++j) {   // one ring per tap: a step's walk is a bump of the two lane addresses, nothing scalar
+        const float* wp = w_lane + (p.flip ? p.K - 1 - j : j);
+        const float* xp = x_lane + j * p.d;
+        ring_run(csteps, [&](int slot) {
+#pragma unroll
+          for (int m = 0; m < M_REP; ++m) wv[slot][m] = wp[m * wrep];
+#pragma unroll
+          for (int n = 0; n < N_REP; ++n) xv[slot][n] = xp[FOLD ? noff[n] : n * 16];
+          wp += 4 * p.K; xp += 4 * p.XS;
+        }, mma);
+      }
     }
-    if (s < nsteps) mma(0);
 
     if (M_REP >= 2 && (needL || needR)) {   // reflect-pad fold (input-grad of a reflect conv): edge waves only
       // Per side, only the 16-column sub-tiles that hold mirrored columns take part (pad <= 25: one or two of them). Each
@@ -395,7 +459,7 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
         }
       }
     }
-    if (M_REP == 1 && (needL || needR)) {   // reflect-pad fold, 16-row tiles: plain loop (one MFMA per step, nothing to pipeline)
+    if (M_REP == 1 && (needL || needR)) {   // reflect-pad fold, 16-row tiles: every sub-tile of the wave, straight into its accumulators
       for (int side = 0; side < 2; ++side) {
         if (side == 0 ? !needL : !needR) continue;
         int mb[N_REP]; bool mv[N_REP];
@@ -405,7 +469,38 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
           if (side == 0) { mv[n] = (u >= 1 && u <= p.mirror && u < p.T); mb[n] = -u - n0 + p.i0; }
           else { mv[n] = (u >= p.T - 1 - p.mirror && u <= p.T - 2 && u >= 0); mb[n] = 2 * (p.T - 1) - u - n0 + p.i0; }
         }
-        for (int j = 0; j < p.K; ++j) {
+        if constexpr (DEPTH > 0) {
+          if (!p.one_ahead) {   // a ring per tap here too: the clamped column and the lanes' `ok` are the tap's
+            int mbv[N_REP];                                  // lanes without a mirrored column: an origin no tap brings into [0, span)
+#pragma unroll
+            for (int n = 0; n < N_REP; ++n) mbv[n] = mv[n] ? mb[n] : -(1 << 28);
+            for (int j = 0; j < p.K; ++j) {
+              const float* wp = w_lane + (p.flip ? p.K - 1 - j : j);
+              const float* xp[N_REP]; bool ok[N_REP];
+#pragma unroll
+              for (int n = 0; n < N_REP; ++n) {
+                const int idx = mbv[n] + j * p.d;
+                ok[n] = (unsigned)idx < (unsigned)p.span;
+                xp[n] = xs + kq * p.XS + (ok[n] ? idx : 0);
+              }
+              ring_run(csteps, [&](int slot) {
+#pragma unroll
+                for (int m = 0; m < M_REP; ++m) wv[slot][m] = wp[m * wrep];
+#pragma unroll
+                for (int n = 0; n < N_REP; ++n) { xv[slot][n] = *xp[n]; xp[n] += 4 * p.XS; }
+                wp += 4 * p.K;
+              }, [&](int slot) {
+#pragma unroll
+                for (int m = 0; m < M_REP; ++m)
+#pragma unroll
+                  for (int n = 0; n < N_REP; ++n)
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(ok[n] ? xv[slot][n] : 0.f, wv[slot][m], acc[m][n], 0, 0, 0);
+              });
+            }
+            continue;
+          }
+        }
+        for (int j = 0; j < p.K; ++j) {   // plain loop (from four MFMAs per step on; test-only for the ring's tiles)
           const float* wj = w_lane + (p.flip ? p.K - 1 - j : j);
           for (int cs = 0; cs < csteps; ++cs) {
             float wm_[M_REP], xm_[N_REP];
@@ -469,6 +564,8 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
         }
       }
     }
+    PROF(6)
+    PROF_END
     return;
   }
   // One float4 of the output: channel co, time steps t0 .. t0+3 (all inside the tensor). Returns the stored values.
@@ -574,6 +671,7 @@ static hipError_t lean_launch3(const LeanP& p, int B, hipStream_t st) {
   TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
   dim3 grid(FOLD ? 1 : (p.T + NT - 1) / NT, (p.Cout + MT - 1) / MT, FOLD ? (B + p.fold - 1) / p.fold : B);
   LeanP q = p; q.swz = g_knob[0] && (long)grid.x * grid.y * grid.z >= 16;
+  q.one_ahead = g_knob[8] != 0;
   const size_t lds = (size_t)(p.xnp * p.xrp * p.XS + p.wnp * p.wrp * p.WS) * sizeof(float);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
   return hipGetLastError();

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 pkg = importlib.import_module('td-vc-gan_amd')
 ops, arena, L = pkg.ops, pkg.arena, pkg._lib
-L.LIB_PATH = os.path.join(os.path.dirname(L.LIB_PATH), 'libtdvc_hip_prof.so')
+L.LIB_PATH = os.environ.get('TDVC_PROF_LIB') or os.path.join(os.path.dirname(L.LIB_PATH), 'libtdvc_hip_prof.so')      # TDVC_PROF_LIB: another commit's `make prof` build
 L.SIGNATURES['tdvc_debug_lean_prof'] = (C.c_int, [C.c_void_p])
 L.SIGNATURES['tdvc_debug_wgrad_prof'] = (C.c_int, [C.c_void_p])
 
@@ -23,7 +23,8 @@ SHAPES = {  # name: (cin, cout, k, dil, T, reflect, pre)
     'c16k3': (16, 16, 3, 1, 16000, True, 1), 'c16k11d5': (16, 16, 11, 5, 16000, True, 1), 'c16k1': (16, 16, 1, 1, 16000, False, 1),
     'c32k7d3': (32, 32, 7, 3, 8000, True, 1), 'c64k11': (64, 64, 11, 1, 4000, True, 1), 'c128k7': (128, 128, 7, 1, 500, True, 1),
     'cond2_c16': (136, 32, 3, 1, 16000, False, 1), 'cond2_c32': (136, 64, 3, 1, 8000, False, 1), 'cond2_c64': (136, 128, 3, 1, 4000, False, 1),
-    'd5': (1024, 1024, 5, 1, 63, False, 0), 'cond2_c64s': (136, 128, 3, 1, 1024, False, 1), 'cond2_c64m': (136, 128, 3, 1, 2048, False, 1),
+    'd5': (1024, 1024, 5, 1, 63, False, 0), 'd5_T32': (1024, 1024, 5, 1, 32, False, 0), 'head1024': (1024, 16, 3, 1, 63, False, 0),
+    'mrf256k7': (256, 256, 7, 1, 50, True, 1), 'c128k11d5': (128, 128, 11, 5, 500, True, 1), 'cond2_c64s': (136, 128, 3, 1, 1024, False, 1), 'cond2_c64m': (136, 128, 3, 1, 2048, False, 1),
 }
 NAMES = ['prologue', 'bar_top', 'commit', 'bar_staged', 'issue', 'mfma', 'epilogue']
 
@@ -90,6 +91,8 @@ def main():
                 for nm, sel in (('end ', (ids == 0) | (ids == nt - 1)), ('mid ', (ids != 0) & (ids != nt - 1))):
                     if sel.any():
                         print(f'     {nm} ' + '  '.join(f'{n}={fb[sel][:, i].mean():8.0f}' for i, n in enumerate(NAMES)) + f'  total={(fb[sel][:, :7].sum(1) + fb[sel][:, 8]).mean():8.0f}  (gx={nt})', flush=True)
+            steps = k * (cin if which == 'fwd' else cout) // 4      # k-steps of a wave over all its chunks (the reflect fold's come on top)
+            print(f'     mfma phase / k-step = {r[:, 5].mean() / steps:6.1f} cycles ({steps} steps)   mfma share of the block = {r[:, 5].mean() / tot.mean():.2f}', flush=True)
             print('     p50  ' + '  '.join(f'{n}={r[:, i].median():8.0f}' for i, n in enumerate(NAMES)) + f'  total p50={tot.median():8.0f} max={tot.max():8.0f}', flush=True)
 
 
