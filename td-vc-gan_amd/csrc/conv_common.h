@@ -27,8 +27,9 @@ extern int g_force_tile;
 extern int g_force_gemm_tile;   // conv_mfma.hip: tests pin the tile of the generic MFMA conv kernel
 extern int g_force_generic;      // conv_api.hip: tests route every conv to the scalar kernels
 extern int g_lds_cap;
-extern int g_knob[9];   // tuning knobs (tdvc_debug_knob): [0] XCD-aware block order of the lean conv kernel (default off: measured null, profiles/r02_e_xcd_remap_ab.txt);
+extern int g_knob[10];   // tuning knobs (tdvc_debug_knob): [0] XCD-aware block order of the lean conv kernel (default off: measured null, profiles/r02_e_xcd_remap_ab.txt);
                         // [8] test-only: the lean conv tiles with a fragment ring run their one-step-ahead loop instead (conv_lean.hip)
+                        // [9] test-only: the lean conv kernel runs its one-float4-at-a-time epilogue instead of the batched one (conv_lean.hip)
 void trace_kernel(const void* fn);
 }
 #define TDVC_TRACE(k) do { if (tdvc::g_trace_on) tdvc::trace_kernel(reinterpret_cast<const void*>(k)); } while (0)
@@ -202,6 +203,16 @@ __device__ __forceinline__ srd_t make_srd(const float* base, int bytes) {   // w
 }
 __device__ __forceinline__ f32x4_t buf_load4(srd_t rs, int voff) {
   return __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
+}
+__device__ __forceinline__ float buf_load1(srd_t rs, int voff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, 0, 0));
+}
+// Stores through the same range check: an offset past the descriptor's end (0x7f000000) drops the store.
+__device__ __forceinline__ void buf_store4(srd_t rs, int voff, f32x4_t v) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), rs, voff, 0, 0);
+}
+__device__ __forceinline__ void buf_store1(srd_t rs, int voff, float v) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, voff, 0, 0);
 }
 
 // Raw buffer loads with an out-of-range offset for the elements that must read as zero: nothing selects on the loaded

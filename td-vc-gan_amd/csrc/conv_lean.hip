@@ -11,6 +11,8 @@
 //   * interior tiles stage through registers one channel chunk ahead of the MFMA loop (T14 split).
 #include "conv_common.h"
 #include "conv_lean.h"
+#include <algorithm>
+#include <type_traits>
 
 PROF_DEFINE(tdvc_debug_lean_prof)
 
@@ -54,6 +56,19 @@ __device__ __forceinline__ float lean_fetch(const LeanP& p, int b, int c, int q)
 constexpr int lean_min_blocks(int m_rep, int n_rep, int wm, int xfk) {
   if (m_rep == 1 && n_rep == 4 && wm == 1 && xfk == LXF_ACT) return 5;   // 16 x 256 tile, plain prologue: 5 resident blocks (<= 96 VGPRs) is what the HBM-bound convs run at
   return m_rep * n_rep >= 9 ? 2 : ((m_rep * n_rep >= 8 || (wm == 4 && xfk == LXF_FILM)) ? 3 : LEAN_OCC_SMALL);   // (FiLM prologue on 64 x 64: 12 spills at 4)
+}
+// Rows (of the wave's M_REP) the epilogue handles per batch: all operand loads of a batch are in flight together, at most 16 float4
+// (64 registers) of them -- the FiLM epilogue has four loaded operands per float4, the others at most two.
+constexpr int lean_epi_rows(int m_rep, int n_rep, int epi) {
+  int r = 16 / (n_rep * (epi == EPI_FILM ? 4 : 2));
+  r = r < 1 ? 1 : (r > m_rep ? m_rep : r);
+  while (m_rep % r) --r;
+  return r;
+}
+// ... and sub-tiles of a row: all of them, but two on the 16 x 256 tile with the FiLM epilogue, whose 96 registers (5 resident blocks)
+// do not hold four float4 with four operands each beside the accumulators (12 bytes of scratch with all four).
+constexpr int lean_epi_cols(int m_rep, int n_rep, int wm, int xfk, int epi) {
+  return (m_rep == 1 && n_rep == 4 && wm == 1 && xfk == LXF_ACT && epi == EPI_FILM) ? 2 : n_rep;
 }
 #ifndef LEAN_RING_1
 #define LEAN_RING_1 2         // fragment sets in flight on the tiles with one MFMA per step (A/B knob: make ab EXTRA=-DLEAN_RING_1=4)
@@ -526,41 +541,127 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
   }
 
   // ---- epilogue: lane owns channel co = .. + ln and time steps t0 .. t0+3 (t0 % 4 == 0, T % 4 == 0)
-  if (!vec_ok) {   // short, unaligned sequences (T = 50, 63): scalar epilogue
+  auto sign_nibble = [](const f32x4& v, const int t0) -> unsigned {   // this float4's sign bits at their place in the 32-step word
+    return ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u)) << (t0 & 31);
+  };
+  if (p.old_epi) {   // test-only (tdvc_debug_knob 9): one float4 at a time, every operand load behind its own test -- the batched epilogue's results are compared with this one's
+    if (!vec_ok) {   // short, unaligned sequences (T = 50, 63): scalar epilogue
 #pragma unroll
-    for (int m = 0; m < M_REP; ++m) {
-      const int co = r0 + wrow0 + m * 16 + ln;
-      if (co >= p.Cout) continue;
-      const long ro = (long)co * p.T;
-      const float bias = (EPI == EPI_FWD && p.bias) ? p.bias[co] : 0.f;
+      for (int m = 0; m < M_REP; ++m) {
+        const int co = r0 + wrow0 + m * 16 + ln;
+        if (co >= p.Cout) continue;
+        const long ro = (long)co * p.T;
+        const float bias = (EPI == EPI_FWD && p.bias) ? p.bias[co] : 0.f;
 #pragma unroll
-      for (int n = 0; n < N_REP; ++n) {
+        for (int n = 0; n < N_REP; ++n) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int t = n0 + wcol0 + n * 16 + kq * 4 + q;
-          if (t >= p.T) continue;
-          const long oi = ro + t;
-          float v = acc[m][n][q];
-          if (EPI == EPI_FWD) {
-            v += bias;
-            if (p.bias3) v += p.bias3[((long)b * p.Cout + co) * 3 + (t == 0 ? 0 : (t == p.T - 1 ? 2 : 1))];
-            if (p.res) v += p.res[(long)b * p.res_bs + oi];
-            if (p.post == POST_LRELU) v = fmaxf(v, v * p.m_slope);
-            else if (p.post == POST_TANH) v = tanhf(v);
-            v *= p.out_scale;
-          } else if (EPI == EPI_MASK) {
-            v = p.mx[(long)b * p.mx_bs + oi] > 0.f ? v : v * p.m_slope;
-          } else if (EPI == EPI_FILM) {
-            const float h = p.mx[(long)b * p.mx_bs + oi];
-            const float* gp = p.gb + (long)b * p.gb_bs + oi;
-            const float ga = gp[0], be = gp[(long)p.Cout * p.T];
-            const float dh2 = (h * (1.f + ga) + be) > 0.f ? v : v * p.m_slope;
-            float* dg = p.dgb + (long)b * p.dgb_bs + oi;
-            dg[0] = dh2 * h; dg[(long)p.Cout * p.T] = dh2;
-            v = dh2 * (1.f + ga);
+          for (int q = 0; q < 4; ++q) {
+            const int t = n0 + wcol0 + n * 16 + kq * 4 + q;
+            if (t >= p.T) continue;
+            const long oi = ro + t;
+            float v = acc[m][n][q];
+            if (EPI == EPI_FWD) {
+              v += bias;
+              if (p.bias3) v += p.bias3[((long)b * p.Cout + co) * 3 + (t == 0 ? 0 : (t == p.T - 1 ? 2 : 1))];
+              if (p.res) v += p.res[(long)b * p.res_bs + oi];
+              if (p.post == POST_LRELU) v = fmaxf(v, v * p.m_slope);
+              else if (p.post == POST_TANH) v = tanhf(v);
+              v *= p.out_scale;
+            } else if (EPI == EPI_MASK) {
+              v = p.mx[(long)b * p.mx_bs + oi] > 0.f ? v : v * p.m_slope;
+            } else if (EPI == EPI_FILM) {
+              const float h = p.mx[(long)b * p.mx_bs + oi];
+              const float* gp = p.gb + (long)b * p.gb_bs + oi;
+              const float ga = gp[0], be = gp[(long)p.Cout * p.T];
+              const float dh2 = (h * (1.f + ga) + be) > 0.f ? v : v * p.m_slope;
+              float* dg = p.dgb + (long)b * p.dgb_bs + oi;
+              dg[0] = dh2 * h; dg[(long)p.Cout * p.T] = dh2;
+              v = dh2 * (1.f + ga);
+            }
+            if (p.add) v += p.add_scale * p.add[(long)b * p.add_bs + oi];
+            p.y[(long)b * p.y_bs + oi] = v;
           }
-          if (p.add) v += p.add_scale * p.add[(long)b * p.add_bs + oi];
-          p.y[(long)b * p.y_bs + oi] = v;
+        }
+      }
+    } else {
+      // One float4 of the output: channel co, time steps t0 .. t0+3 (all inside the tensor). Returns the stored values.
+      auto epi_store = [&](f32x4 v, const int co, const int t0, const float bias, const int b) -> f32x4 {     // b: the sample (shadows the block's)
+        const long oi = (long)co * p.T + t0;
+        if (EPI == EPI_FWD) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] += bias;
+          if (p.bias3) {
+            const float* k3 = p.bias3 + ((long)b * p.Cout + co) * 3;
+            const float mid = k3[1];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] += mid;
+            if (t0 == 0) v[0] += k3[0] - mid;
+            if (t0 + 4 == p.T) v[3] += k3[2] - mid;
+          }
+          if (p.res) { const f32x4 r = *reinterpret_cast<const f32x4*>(p.res + (long)b * p.res_bs + oi); v += r; }
+          if (p.post == POST_LRELU) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], v[q] * p.m_slope);
+          } else if (p.post == POST_TANH) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
+          }
+          v *= p.out_scale;
+        } else if (EPI == EPI_MASK) {
+          if (N_REP >= 2 && p.mbits) {   // sign bits instead of the fp32 mask source: one word per 32 time steps (host: T % 32 == 0)
+            const unsigned wbits = p.mbits[(long)b * p.mb_bs + (long)co * (p.T >> 5) + (t0 >> 5)] >> (t0 & 31);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = ((wbits >> q) & 1u) ? v[q] : v[q] * p.m_slope;
+          } else {
+            const f32x4 mm = *reinterpret_cast<const f32x4*>(p.mx + (long)b * p.mx_bs + oi);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = mm[q] > 0.f ? v[q] : v[q] * p.m_slope;
+          }
+        } else if (EPI == EPI_FILM) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(p.mx + (long)b * p.mx_bs + oi);
+          const float* gp = p.gb + (long)b * p.gb_bs + oi;
+          const f32x4 ga = *reinterpret_cast<const f32x4*>(gp);
+          const f32x4 be = *reinterpret_cast<const f32x4*>(gp + (long)p.Cout * p.T);
+          f32x4 dga, dbe;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float h2 = h[q] * (1.f + ga[q]) + be[q];
+            const float dh2 = h2 > 0.f ? v[q] : v[q] * p.m_slope;
+            dga[q] = dh2 * h[q]; dbe[q] = dh2; v[q] = dh2 * (1.f + ga[q]);
+          }
+          float* dg = p.dgb + (long)b * p.dgb_bs + oi;
+          *reinterpret_cast<f32x4*>(dg) = dga;
+          *reinterpret_cast<f32x4*>(dg + (long)p.Cout * p.T) = dbe;
+        }
+        if (p.add) { const f32x4 a4 = *reinterpret_cast<const f32x4*>(p.add + (long)b * p.add_bs + oi); v += a4 * p.add_scale; }
+        *reinterpret_cast<f32x4*>(p.y + (long)b * p.y_bs + oi) = v;
+        return v;
+      };
+#pragma unroll
+      for (int m = 0; m < M_REP; ++m) {
+        const int co = r0 + wrow0 + m * 16 + ln;
+        if (co >= p.Cout) continue;
+        float bias = 0.f;
+        if (EPI == EPI_FWD && p.bias) bias = p.bias[co];
+        unsigned sb_word = 0;
+#pragma unroll
+        for (int n = 0; n < N_REP; ++n) {
+          int t0 = n0 + wcol0 + n * 16 + kq * 4, bb = b;
+          if (FOLD) { const int sg = t0 / p.T; t0 -= sg * p.T; bb = b + sg; if (bb >= p.Bn) continue; }
+          if (t0 >= p.T) continue;
+          const f32x4 v = epi_store(acc[m][n], co, t0, bias, bb);
+          if (EPI == EPI_FWD && N_REP >= 2 && p.sbits) {
+            // sign bits of the stored values: the 4 lanes (kq = 0..3) of a channel are OR-ed with two wave shuffles, and sub-tiles
+            // (n, n+1) make one 32-bit word (the wave's first column is a multiple of 32: 16 * N_REP columns per wave, N_REP even)
+            const unsigned h = sign_nibble(v, t0);
+            sb_word = (n & 1) ? (sb_word | h) : h;
+            if (n & 1) {
+              unsigned w = sb_word;
+              w |= (unsigned)__shfl_xor((int)w, 16);
+              w |= (unsigned)__shfl_xor((int)w, 32);
+              if (kq == 0) p.sbits[(long)b * p.sb_bs + (long)co * (p.T >> 5) + (t0 >> 5)] = w;
+            }
+          }
         }
       }
     }
@@ -568,89 +669,185 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
     PROF_END
     return;
   }
-  // One float4 of the output: channel co, time steps t0 .. t0+3 (all inside the tensor). Returns the stored values.
-  auto epi_store = [&](f32x4 v, const int co, const int t0, const float bias, const int b) -> f32x4 {     // b: the sample (shadows the block's)
-    const long oi = (long)co * p.T + t0;
-    if (EPI == EPI_FWD) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] += bias;
-      if (p.bias3) {
-        const float* k3 = p.bias3 + ((long)b * p.Cout + co) * 3;
-        const float mid = k3[1];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] += mid;
-        if (t0 == 0) v[0] += k3[0] - mid;
-        if (t0 + 4 == p.T) v[3] += k3[2] - mid;
-      }
-      if (p.res) { const f32x4 r = *reinterpret_cast<const f32x4*>(p.res + (long)b * p.res_bs + oi); v += r; }
-      if (p.post == POST_LRELU) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], v[q] * p.m_slope);
-      } else if (p.post == POST_TANH) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
-      }
-      v *= p.out_scale;
-    } else if (EPI == EPI_MASK) {
-      if (N_REP >= 2 && p.mbits) {   // sign bits instead of the fp32 mask source: one word per 32 time steps (host: T % 32 == 0)
-        const unsigned wbits = p.mbits[(long)b * p.mb_bs + (long)co * (p.T >> 5) + (t0 >> 5)] >> (t0 & 31);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = ((wbits >> q) & 1u) ? v[q] : v[q] * p.m_slope;
-      } else {
-        const f32x4 mm = *reinterpret_cast<const f32x4*>(p.mx + (long)b * p.mx_bs + oi);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = mm[q] > 0.f ? v[q] : v[q] * p.m_slope;
-      }
-    } else if (EPI == EPI_FILM) {
-      const f32x4 h = *reinterpret_cast<const f32x4*>(p.mx + (long)b * p.mx_bs + oi);
-      const float* gp = p.gb + (long)b * p.gb_bs + oi;
-      const f32x4 ga = *reinterpret_cast<const f32x4*>(gp);
-      const f32x4 be = *reinterpret_cast<const f32x4*>(gp + (long)p.Cout * p.T);
-      f32x4 dga, dbe;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float h2 = h[q] * (1.f + ga[q]) + be[q];
-        const float dh2 = h2 > 0.f ? v[q] : v[q] * p.m_slope;
-        dga[q] = dh2 * h[q]; dbe[q] = dh2; v[q] = dh2 * (1.f + ga[q]);
-      }
-      float* dg = p.dgb + (long)b * p.dgb_bs + oi;
-      *reinterpret_cast<f32x4*>(dg) = dga;
-      *reinterpret_cast<f32x4*>(dg + (long)p.Cout * p.T) = dbe;
-    }
-    if (p.add) { const f32x4 a4 = *reinterpret_cast<const f32x4*>(p.add + (long)b * p.add_bs + oi); v += a4 * p.add_scale; }
-    *reinterpret_cast<f32x4*>(p.y + (long)b * p.y_bs + oi) = v;
-    return v;
+  // Batched epilogue. A batch is EB rows of the wave's sub-tiles (lean_epi_rows: the whole tile on the 16-row tiles). The loads of a
+  // whole batch go out first, then each float4 is computed and stored in the old order, with the old expressions. No load and no
+  // store stands behind a branch: a lane past Cout, past T or past the last sample of a folded group carries an out-of-range buffer
+  // offset instead, which loads zeros and drops the store. What changes the code is resolved once per block, in front of the batches,
+  // and each answer enters its own straight-line code: float4 or dword accesses, with or without add, fp32 or 1-bit mask, the
+  // post-activation. (add is part of the code because `v * scale + add * add_scale` contracts to another FMA when v has a second
+  // use.) The forward's res and bias3 only ever follow additions: an absent one has an empty descriptor, so its loads fetch nothing,
+  // and its term is kept out of the sum by a select on the wave-uniform flag (no added zero: -0.0 + 0.0 would move a bit).
+  // (Tested per float4, on pointers that may alias the stores, every operand load was followed by s_waitcnt vmcnt(0) -- which on
+  // this ISA also waits for the store in front: up to 32 exposed memory round trips per wave behind the last MFMA.) The scalar path
+  // (rows not 16-byte aligned: T = 50, 63) runs the same batches with four dword accesses per operand.
+  constexpr int EB = lean_epi_rows(M_REP, N_REP, EPI), NB = lean_epi_cols(M_REP, N_REP, WM, XFK, EPI);
+  constexpr int OOR = 0x7f000000;
+  const int ct = p.Cout * p.T;
+  const int nsamp = FOLD ? min(p.fold, p.Bn - b) : 1;      // samples of the tile that exist
+  const bool has_res = EPI == EPI_FWD && p.res != nullptr, has_b3 = EPI == EPI_FWD && p.bias3 != nullptr;
+  auto srd_of = [&](const float* base, int bs, bool has) __attribute__((always_inline)) {   // one [B][Cout][T] operand over the tile's samples
+    return make_srd(has ? base + (long)b * bs : nullptr, has ? ((nsamp - 1) * bs + ct) * 4 : 0);
   };
-  auto sign_nibble = [](const f32x4& v, const int t0) -> unsigned {   // this float4's sign bits at their place in the 32-step word
-    return ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u)) << (t0 & 31);
-  };
-
+  auto epilogue = [&](auto VEC_, auto ADD_, auto BITS_, auto POST_) __attribute__((always_inline)) {
+    constexpr bool VEC = decltype(VEC_)::value, ADD = decltype(ADD_)::value, BITS = decltype(BITS_)::value;
+    constexpr int POST = decltype(POST_)::value;
+    constexpr bool MX = (EPI == EPI_MASK && !BITS) || EPI == EPI_FILM;
+    const srd_t sy = srd_of(p.y, p.y_bs, true), sadd = srd_of(p.add, p.add_bs, ADD), sres = srd_of(p.res, p.res_bs, has_res);
+    const srd_t smx = srd_of(p.mx, p.mx_bs, MX);
+    const srd_t sga = srd_of(p.gb, p.gb_bs, EPI == EPI_FILM), sbe = srd_of(p.gb + ct, p.gb_bs, EPI == EPI_FILM);
+    const srd_t sdg = srd_of(p.dgb, p.dgb_bs, EPI == EPI_FILM), sdb = srd_of(p.dgb + ct, p.dgb_bs, EPI == EPI_FILM);
+    const srd_t sbit = make_srd(BITS ? reinterpret_cast<const float*>(p.mbits + (long)b * p.mb_bs) : nullptr, BITS ? p.Cout * (p.T >> 5) * 4 : 0);
+    const srd_t sbias = make_srd(p.bias, (EPI == EPI_FWD && p.bias) ? p.Cout * 4 : 0);
+    const srd_t sb3 = make_srd(has_b3 ? p.bias3 + (long)b * p.Cout * 3 : nullptr, has_b3 ? nsamp * p.Cout * 12 : 0);
+    // a float4 (VEC) or its four dwords, each inside the row or out of range
+    auto ld = [&](const srd_t s, const int o, const int t0) __attribute__((always_inline)) -> f32x4 {
+      if constexpr (VEC) return buf_load4(s, o);
+      else {
+        f32x4 r;
 #pragma unroll
-  for (int m = 0; m < M_REP; ++m) {
-    const int co = r0 + wrow0 + m * 16 + ln;
-    if (co >= p.Cout) continue;
-    float bias = 0.f;
-    if (EPI == EPI_FWD && p.bias) bias = p.bias[co];
-    unsigned sb_word = 0;
+        for (int q = 0; q < 4; ++q) r[q] = buf_load1(s, (o != OOR && t0 + q < p.T) ? o + 4 * q : OOR);
+        return r;
+      }
+    };
+    auto st = [&](const srd_t s, const int o, const int t0, const f32x4 v) __attribute__((always_inline)) {
+      if constexpr (VEC) buf_store4(s, o, v);
+      else {
 #pragma unroll
-    for (int n = 0; n < N_REP; ++n) {
-      int t0 = n0 + wcol0 + n * 16 + kq * 4, bb = b;
-      if (FOLD) { const int sg = t0 / p.T; t0 -= sg * p.T; bb = b + sg; if (bb >= p.Bn) continue; }
-      if (t0 >= p.T) continue;
-      const f32x4 v = epi_store(acc[m][n], co, t0, bias, bb);
-      if (EPI == EPI_FWD && N_REP >= 2 && p.sbits) {
-        // sign bits of the stored values: the 4 lanes (kq = 0..3) of a channel are OR-ed with two wave shuffles, and sub-tiles
-        // (n, n+1) make one 32-bit word (the wave's first column is a multiple of 32: 16 * N_REP columns per wave, N_REP even)
-        const unsigned h = sign_nibble(v, t0);
-        sb_word = (n & 1) ? (sb_word | h) : h;
-        if (n & 1) {
-          unsigned w = sb_word;
-          w |= (unsigned)__shfl_xor((int)w, 16);
-          w |= (unsigned)__shfl_xor((int)w, 32);
-          if (kq == 0) p.sbits[(long)b * p.sb_bs + (long)co * (p.T >> 5) + (t0 >> 5)] = w;
+        for (int q = 0; q < 4; ++q) buf_store1(s, (o != OOR && t0 + q < p.T) ? o + 4 * q : OOR, v[q]);
+      }
+    };
+#pragma unroll
+    for (int m0 = 0; m0 < M_REP; m0 += EB) {
+      int tt[N_REP], sg[N_REP], off[EB][N_REP];
+      bool ok[EB][N_REP];
+      f32x4 vmx[EB][N_REP], vadd[EB][N_REP], vres[EB][N_REP], vga[EB][N_REP], vbe[EB][N_REP];
+      unsigned wb[EB][N_REP];
+      float bias[EB], k3v[EB][FOLD ? N_REP : 1][3];      // bias and bias3: once per row and sample
+      // byte offset of the float4 in an operand with batch stride bs
+      auto at = [&](int mi, int n, int bs) __attribute__((always_inline)) { return FOLD ? (ok[mi][n] ? off[mi][n] + sg[n] * bs * 4 : OOR) : off[mi][n]; };
+#pragma unroll
+      for (int n = 0; n < N_REP; ++n) {
+        tt[n] = n0 + wcol0 + n * 16 + kq * 4; sg[n] = 0;
+        if (FOLD) { sg[n] = tt[n] / p.T; tt[n] -= sg[n] * p.T; }
+      }
+#pragma unroll
+      for (int nb = 0; nb < N_REP; nb += NB) {
+        // ---- issue: every load of the batch
+#pragma unroll
+        for (int mi = 0; mi < EB; ++mi) {
+          const int co = r0 + wrow0 + (m0 + mi) * 16 + ln;
+          if (EPI == EPI_FWD && nb == 0) {
+            bias[mi] = buf_load1(sbias, co * 4);
+#pragma unroll
+            for (int s = 0; s < (FOLD ? N_REP : 1); ++s)
+#pragma unroll
+              for (int e = 0; e < 3; ++e)
+                k3v[mi][s][e] = buf_load1(sb3, (co < p.Cout && sg[s] < nsamp) ? ((sg[s] * p.Cout + co) * 3 + e) * 4 : OOR);
+          }
+#pragma unroll
+          for (int n = nb; n < nb + NB; ++n) {
+            ok[mi][n] = co < p.Cout && tt[n] < p.T && (!FOLD || sg[n] < nsamp);
+            off[mi][n] = ok[mi][n] ? (co * p.T + tt[n]) * 4 : OOR;
+            if (EPI == EPI_FWD) vres[mi][n] = ld(sres, at(mi, n, p.res_bs), tt[n]);
+            if constexpr (BITS) wb[mi][n] = __builtin_bit_cast(unsigned, buf_load1(sbit, ok[mi][n] ? (co * (p.T >> 5) + (tt[n] >> 5)) * 4 : OOR));
+            if constexpr (MX) vmx[mi][n] = ld(smx, at(mi, n, p.mx_bs), tt[n]);
+            if (EPI == EPI_FILM) { vga[mi][n] = ld(sga, at(mi, n, p.gb_bs), tt[n]); vbe[mi][n] = ld(sbe, at(mi, n, p.gb_bs), tt[n]); }
+            if constexpr (ADD) vadd[mi][n] = ld(sadd, at(mi, n, p.add_bs), tt[n]);
+          }
+        }
+        // ---- consume: the old arithmetic, float4 by float4
+#pragma unroll
+        for (int mi = 0; mi < EB; ++mi) {
+          const int co = r0 + wrow0 + (m0 + mi) * 16 + ln;
+          unsigned sb_word = 0;
+#pragma unroll
+          for (int n = nb; n < nb + NB; ++n) {
+            const int t0 = tt[n];
+            f32x4 v = acc[m0 + mi][n];
+            if (EPI == EPI_FWD) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[q] += bias[mi];
+              const float* k3 = k3v[mi][FOLD ? n : 0];
+              if constexpr (VEC) {
+                const float mid = k3[1];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = has_b3 ? v[q] + mid : v[q];
+                v[0] = (has_b3 && t0 == 0) ? v[0] + (k3[0] - mid) : v[0];
+                v[3] = (has_b3 && t0 + 4 == p.T) ? v[3] + (k3[2] - mid) : v[3];
+              } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = has_b3 ? v[q] + (t0 + q == 0 ? k3[0] : (t0 + q == p.T - 1 ? k3[2] : k3[1])) : v[q];
+              }
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[q] = has_res ? v[q] + vres[mi][n][q] : v[q];
+              if constexpr (POST == POST_LRELU) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], v[q] * p.m_slope);
+              } else if constexpr (POST == POST_TANH) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = tanhf(v[q]);
+              }
+              v *= p.out_scale;
+            } else if (EPI == EPI_MASK) {
+              if constexpr (BITS) {   // sign bits instead of the fp32 mask source: one word per 32 time steps (host: T % 32 == 0)
+                const unsigned wbits = wb[mi][n] >> (t0 & 31);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = ((wbits >> q) & 1u) ? v[q] : v[q] * p.m_slope;
+              } else {
+                const f32x4 mm = vmx[mi][n];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[q] = mm[q] > 0.f ? v[q] : v[q] * p.m_slope;
+              }
+            } else if (EPI == EPI_FILM) {
+              const f32x4 h = vmx[mi][n], ga = vga[mi][n], be = vbe[mi][n];
+              f32x4 dga, dbe;
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                const float h2 = h[q] * (1.f + ga[q]) + be[q];
+                const float dh2 = h2 > 0.f ? v[q] : v[q] * p.m_slope;
+                dga[q] = dh2 * h[q]; dbe[q] = dh2; v[q] = dh2 * (1.f + ga[q]);
+              }
+              st(sdg, at(mi, n, p.dgb_bs), t0, dga);
+              st(sdb, at(mi, n, p.dgb_bs), t0, dbe);
+            }
+            if constexpr (ADD) v += vadd[mi][n] * p.add_scale;
+            st(sy, at(mi, n, p.y_bs), t0, v);
+            if (EPI == EPI_FWD && N_REP >= 2 && p.sbits) {
+              // sign bits of the stored values: the 4 lanes (kq = 0..3) of a channel are OR-ed with two wave shuffles, and sub-tiles
+              // (n, n+1) make one 32-bit word (the wave's first column is a multiple of 32: 16 * N_REP columns per wave, N_REP even)
+              const unsigned h = sign_nibble(v, t0);
+              sb_word = (n & 1) ? (sb_word | h) : h;
+              if (n & 1) {
+                unsigned w = sb_word;
+                w |= (unsigned)__shfl_xor((int)w, 16);
+                w |= (unsigned)__shfl_xor((int)w, 32);
+                if (kq == 0 && ok[mi][n]) p.sbits[(long)b * p.sb_bs + (long)co * (p.T >> 5) + (t0 >> 5)] = w;
+              }
+            }
+          }
         }
       }
     }
+  };
+  // what changes the code: wave-uniform, resolved here once
+  constexpr std::false_type NO{};
+  constexpr std::true_type YES{};
+  constexpr std::integral_constant<int, POST_NONE> P0{};
+  auto by_kind = [&](auto V, auto A) __attribute__((always_inline)) {
+    if constexpr (EPI == EPI_FWD) {
+      if (p.post == POST_LRELU) epilogue(V, A, NO, std::integral_constant<int, POST_LRELU>{});
+      else if (p.post == POST_TANH) epilogue(V, A, NO, std::integral_constant<int, POST_TANH>{});
+      else epilogue(V, A, NO, P0);
+    } else if constexpr (EPI == EPI_MASK && N_REP >= 2 && decltype(V)::value) {
+      if (p.mbits) epilogue(V, A, YES, P0); else epilogue(V, A, NO, P0);
+    } else {
+      epilogue(V, A, NO, P0);
+    }
+  };
+  if (FOLD || vec_ok) {      // folded tiles are float4 only (host)
+    if (p.add) by_kind(YES, YES); else by_kind(YES, NO);
+  } else if constexpr (!FOLD) {
+    if (p.add) by_kind(NO, YES); else by_kind(NO, NO);
   }
   PROF(6)
   PROF_END
@@ -672,6 +869,7 @@ static hipError_t lean_launch3(const LeanP& p, int B, hipStream_t st) {
   dim3 grid(FOLD ? 1 : (p.T + NT - 1) / NT, (p.Cout + MT - 1) / MT, FOLD ? (B + p.fold - 1) / p.fold : B);
   LeanP q = p; q.swz = g_knob[0] && (long)grid.x * grid.y * grid.z >= 16;
   q.one_ahead = g_knob[8] != 0;
+  q.old_epi = g_knob[9] != 0;
   const size_t lds = (size_t)(p.xnp * p.xrp * p.XS + p.wnp * p.wrp * p.WS) * sizeof(float);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
   return hipGetLastError();
@@ -721,6 +919,7 @@ hipError_t launch_conv_lean_cond(LeanP p, int B, hipStream_t st) {
   if (lds > (size_t)(g_lds_cap > 0 ? g_lds_cap : 80 * 1024) || p.wnp > (MT >= 48 ? 10 : 6)) lds = geom(Cc = 16);
   dim3 grid((p.T + NT - 1) / NT, (p.Cout + MT - 1) / MT, B);
   p.swz = g_knob[0] && (long)grid.x * grid.y * grid.z >= 16;
+  p.old_epi = g_knob[9] != 0;
   if (MT == 32) {
     auto k = conv_lean_kernel<2, 4, 1, 4, LXF_COND, EPI_FWD>;
     TDVC_BIG_LDS_ONCE(k); TDVC_TRACE(k);
@@ -781,7 +980,8 @@ hipError_t launch_conv_lean(LeanP p, int B, int xfk, int epi, hipStream_t st) {
   p.fold = 1; p.seg = 0; p.Bn = B;
   const bool fold_combo = (xfk == LXF_ACT && (epi == EPI_FWD || epi == EPI_PLAIN)) || (xfk == LXF_MASK_LRELU && epi == EPI_PLAIN);
   if (g_knob[4] == 0 && g_force_tile < 0 && NT == 64 && R >= 32 && (p.T == 16 || p.T == 32) && p.Cin % 16 == 0 && B >= 64 / p.T && p.vec && !p.reflect && p.mirror == 0 && fold_combo &&
-      !p.sbits && !p.mbits && (!p.aux || p.aux_bs == p.x_bs) && (long)(64 / p.T) * p.x_bs < (1L << 28)) {
+      !p.sbits && !p.mbits && (!p.aux || p.aux_bs == p.x_bs) && (long)(64 / p.T) * p.x_bs < (1L << 28) &&
+      (long)(64 / p.T) * std::max(p.y_bs, std::max(p.res ? p.res_bs : 0, p.add ? p.add_bs : 0)) < (1L << 28)) {   // the epilogue's 32-bit offsets span the group too
     p.fold = 64 / p.T;
     p.seg = ((p.T + hi - lo) + 3) / 4 * 4;
     p.span = p.fold * p.seg;
