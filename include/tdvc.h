@@ -1002,6 +1002,99 @@ int tdvc_crepe_frames_bwd(const float* signal, int64_t s_bs, int32_t T, int32_t 
                           int64_t d_bs, void* workspace, size_t workspace_bytes, void* stream);
 int tdvc_roll_bins(const float* x, int64_t x_bs, int64_t x_cs, const int64_t* shift, float* y, int32_t B, int32_t C, int32_t F, void* stream);
 
+/* The Whisper ASR metric (csrc/asr_whisper.hip): the transcripts that the reference's test_scripts/common/test_asr.py takes from
+ * WhisperForConditionalGeneration("openai/whisper-medium").generate with a forced language and task, greedy, before WER and CER.
+ * The definition is HF transformers' WhisperForConditionalGeneration in eval mode plus WhisperFeatureExtractor's numpy path, restated
+ * here; it is pinned to that implementation's own float64 output on a small seeded configuration (tests/golden/whisper_small.npz,
+ * tools/make_golden_whisper.py) and restated in float64 in tests/whisper_ref.py. No checkpoint is available and none is shipped:
+ * PARITY WITH A REAL WHISPER-MEDIUM CHECKPOINT IS UNCHECKED. d_model is a multiple of 16 up to 1024 (whisper-large, d = 1280, is
+ * refused), head widths 16, 32, 64. The tokenizer and Whisper's text normaliser are not reproduced: ids in, ids out.
+ *   1. Features: a 16 kHz row, zero-padded or truncated to n_samples = chunk_length 16000; per-row device lengths mark where the
+ *      zeros start. Periodic Hann window of 400, hop 160, center=True with reflect padding of 200, the last frame dropped:
+ *      n_samples / 160 frames. Power spectrum over 201 bins, the Slaney-scale, Slaney-normalised mel filter bank (80 bands, 0 to
+ *      8000 Hz; the table is built on the host in float64), log10(max(., 1e-10)), max(., rowmax - 8) with rowmax over the whole row's
+ *      [n_mels][frames], (. + 4) / 4. Float64 inside, one rounding at the store. (HF's numpy path stores the spectrum as complex64
+ *      before the power and rounds the log10 values to float32 before the clamp, which it then evaluates in float32; the definition
+ *      does neither, and differs from HF's values by those roundings: below 2.5e-7 per value.)
+ *   2. Encoder: gelu(conv1) (k 3, pad 1, n_mels -> d), gelu(conv2) (k 3, stride 2, pad 1) + embed_positions.weight (from the state
+ *      dict), then encoder_layers pre-norm layers x += out_proj(attn(LN(x))) with q = (h Wq^T + bq) d_h^-1/2, k = h Wk^T WITHOUT bias,
+ *      v = h Wv^T + bv and a plain softmax, x += fc2(gelu(fc1(LN(x)))); a final layer_norm. LayerNorm eps 1e-5, erf-GELU.
+ *      T_enc = frames / 2. The convolutions, projections and norms are tdvc_wavlm_gemm and tdvc_wavlm_layernorm.
+ *   3. Decoder step at position p for token t: x = embed_tokens[t] + embed_positions[p] (scale_embedding false); per layer causal
+ *      self-attention over the cache positions 0 .. p (this step's k and v appended), cross-attention over the T_enc encoder keys and
+ *      values (projected once per utterance with encoder_attn.k_proj / v_proj), the MLP; the final layer_norm and
+ *      logits = x embed_tokens^T (the tied proj_out, no bias).
+ *   4. Greedy generation: prompt_ids [P] go through the same step with the pick forced; then the argmax with the lowest index on
+ *      ties, after -inf on the `suppress` tokens at every step and on the `begin_suppress` tokens at the first generated step (both as
+ *      one byte mask [vocab]: bit 0 always, bit 1 at the first generated step); a row that has emitted eos emits pad from then on.
+ *      ids [B][P + max_new_tokens], n_tokens [B] (prompt and eos included). No beams, temperature fallback, timestamps or long-form
+ *      chunking; audio past chunk_length is truncated.
+ *   5. WER / CER are host functions on strings (td-vc-gan_amd/whisper.py); text never lives on the device.
+ * The step launches take B <= 16 rows and read the position p from a DEVICE counter: one step is the same launch sequence for every
+ * p, a linear chain, without host synchronisation, and can be captured into a graph once and replayed. No atomics, fixed summation
+ * orders: bit-identical from call to call, and a row in a batch gets the bits it gets alone.
+ * tdvc_whisper_log_mel: item 1. x [B] rows of L samples (x_bs apart), lengths [B] or NULL (samples at and past min(lengths[b], L,
+ *   n_samples) are never read), table = float64 cos[400] | sin[400] | window[400] | filterbank[n_mels][201] ->
+ *   y[b y_bs + m y_ms + f y_fs] fp32, m < n_mels, f < n_samples / 160. Two launches (the row maximum needs the first to end);
+ *   workspace from tdvc_whisper_log_mel_workspace.
+ * tdvc_whisper_attention: q, k, v at p[b bs + t ts + n d + c] (q already scaled) -> out[b][t][n d + c] = sum_s softmax_s(q_t . k_s) v_s:
+ *   the tile of tdvc_wavlm_attention without gate and bias table, T <= 4096.
+ * tdvc_whisper_embed: x[b][:] = embed_tokens[ids[b][p]] + embed_positions[p], p = *pos (clamped to max_pos - 1, ids to the vocabulary).
+ * tdvc_whisper_linear_step: y[b][n] = epilogue((LN?(x[b]) . w[n] + bias[n]) scale_n) [+ res[b][n]], b < B <= 16, w [N][K], exact fp32 on
+ *   v_mfma_f32_16x16x4_f32 with the batch as the MFMA's 16 rows. The weights go from global memory straight to registers (each is
+ *   used once); only the input rows sit in LDS; K is split over the 8 waves of a workgroup in pieces of 128 and the waves' sums are
+ *   added in the order 0 .. 7. gamma, beta: the LayerNorm prologue over the row (K <= 1024, float64 statistics, one rounding,
+ *   recomputed per workgroup). epilogue 0: none, 1: erf-GELU (before the residual). With k_cache the columns n >= cache_lo are k | v of
+ *   width (N - cache_lo) / 2 each and go to cache[b c_bs + p (N - cache_lo) / 2 + c], p = *pos, instead of y. y must not be x; res
+ *   may be y. There is no split of K across workgroups: a launch with N = d has d / 16 workgroups.
+ * tdvc_whisper_attn_step: out[b][n d + c] = sum_s softmax_s(q[b][n d :] . k[b][s][n d :]) v[b][s][n d + c] over s < len' keys,
+ *   len' = min(*pos + 1, len) with pos, else len; k, v at p[b kv_bs + s kv_ts + n d + c]. Keys at and past len' are never read.
+ *   A workgroup per (row, head); the keys are split over 8 waves whose running maxima and sums are combined in the order 0 .. 7.
+ * tdvc_whisper_logits: LN(x) embed_tokens^T through the same kernel, any vocab (the last column tile may be partial). logits (may be
+ *   NULL) receives the raw values; the partials receive, per workgroup and row, the (max, lowest argmax) after the mask of item 4
+ *   (mask may be NULL), the first generated step being *pos == n_prompt - 1.
+ * tdvc_whisper_pick: reduces the partials in a fixed order with lowest-index ties and, with p = *pos: p + 1 < n_prompt keeps the
+ *   prompt token ids[b][p + 1]; else ids[b][p + 1] = finished[b] ? pad : argmax, and an eos sets finished[b]; n_tokens[b] = p + 2
+ *   for a row that was not finished; all_done[0] = every row finished; *pos = p + 1. Nothing happens once p + 1 >= total.
+ * tdvc_whisper_workspace: the bytes of the self-attention cache (2 layers B max_len d floats), the cross keys and values
+ *   (2 layers B T_enc d floats) and the partials; offsets[0..2] receive where each starts, offsets[3] the partials per row.
+ * TDVC_EINVAL: negative sizes or strides, null pointers where not allowed, strides that are not multiples of 4 floats, operands that
+ * are not 16-byte aligned, a row stride below the row's width, a cache row shorter than its positions, a short workspace, y == x.
+ * TDVC_EUNSUPPORTED: d, N or K not a multiple of 16, d (or a LayerNorm row) above 1024, a head width outside {16, 32, 64}, B > 16 in a
+ * step launch, more than 4096 keys, n_samples not a multiple of 160 or below 400, more than 128 mel bands. All before any launch;
+ * B == 0 is a no-op. Whether p stays inside the cache is the host's to know (P + max_new_tokens <= max_target_positions is checked
+ * in whisper.py); the kernels clamp p instead of writing out of bounds. */
+typedef struct {
+  int32_t B, N, K, epilogue, scale_lo, scale_hi;
+  float scale;
+  const float* x; int64_t x_bs;
+  const float* gamma; const float* beta;      /* both or neither */
+  const float* w;                             /* [N][K] */
+  const float* bias;                          /* [N] or NULL */
+  const float* res; int64_t r_bs;             /* NULL: no residual */
+  float* y; int64_t y_bs;
+  int32_t cache_lo, cache_len;                /* with k_cache: first cached column, positions per cache row */
+  const int32_t* pos;
+  float* k_cache; float* v_cache; int64_t c_bs;
+} tdvc_whisper_linear_args;
+size_t tdvc_whisper_log_mel_workspace(int32_t B, int32_t n_samples, int32_t n_mels);
+int tdvc_whisper_log_mel(const float* x, int64_t x_bs, const int32_t* lengths, int32_t B, int32_t L, int32_t n_samples, const double* table,
+                         int32_t n_mels, float* y, int64_t y_bs, int64_t y_ms, int64_t y_fs, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int tdvc_whisper_attention(const float* q, const float* k, const float* v, int64_t bs, int64_t ts, int32_t B, int32_t T, int32_t H, int32_t d,
+                           float* out, int64_t o_bs, int64_t o_ts, void* stream);
+int tdvc_whisper_embed(const int32_t* ids, int64_t ids_ld, const int32_t* pos, int32_t max_pos, const float* embed_tokens,
+                       const float* embed_positions, int32_t B, int32_t d, int32_t vocab, float* x, int64_t x_bs, void* stream);
+int tdvc_whisper_linear_step(const tdvc_whisper_linear_args* args, void* stream);
+int tdvc_whisper_attn_step(const float* q, int64_t q_bs, const float* k, const float* v, int64_t kv_bs, int64_t kv_ts, const int32_t* pos,
+                           int32_t len, int32_t B, int32_t H, int32_t d, float* out, int64_t o_bs, void* stream);
+size_t tdvc_whisper_workspace(int32_t d, int32_t decoder_layers, int32_t vocab, int32_t B, int32_t T_enc, int32_t max_len, int64_t* offsets);
+int tdvc_whisper_logits(const float* x, int64_t x_bs, const float* gamma, const float* beta, const float* embed_tokens, int32_t B, int32_t d,
+                        int32_t vocab, const uint8_t* mask, const int32_t* pos, int32_t n_prompt, float* logits, int64_t l_bs, void* partials,
+                        size_t partial_bytes, void* stream);
+int tdvc_whisper_pick(const void* partials, size_t partial_bytes, int32_t vocab, int32_t B, int32_t* ids, int64_t ids_ld, int32_t n_prompt,
+                      int32_t total, int32_t eos, int32_t pad, int32_t* pos, int32_t* n_tokens, int32_t* finished, int32_t* all_done, void* stream);
+
 int tdvc_contrastive_fwd_bwd(const float* X,const float* Y, const int32_t* idx_x, const int32_t* idx_y, int B, int C, int T, int N,
                              float weight, float* loss_out, float* dX, float* dY, void* stream);
 

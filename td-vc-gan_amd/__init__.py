@@ -18,7 +18,9 @@ Drop-in surface (same names / signatures / state_dict keys as the reference, SUR
     the CREPE pitch tracker of util/crepe.py (torchcrepe's tiny / full network, its front end and its argmax, weighted-argmax and
     Viterbi decoders) as Crepe / load_crepe / crepe_frames / crepe_decode / crepe_transition / get_shift (crepe.py), and the
     activation-MSE F0 term of train.py:439-470 on it as losses.f0_crepe_loss / activation_mse / Crepe.activations_with_grad, with the
-    target of train.py:245-252 as conversion_target / roll_bins (StepConfig.f0_loss='activation').
+    target of train.py:245-252 as conversion_target / roll_bins (StepConfig.f0_loss='activation'), and the intelligibility metric
+    of test_scripts/common/test_asr.py (Whisper's log-mel features, encoder and greedy decoder, WER / CER) as Whisper / WhisperConfig /
+    load_whisper / whisper_log_mel / asr_wer / asr_cer / asr_report (whisper.py).
 
 The HIP library (csrc/ -> libtdvc_hip.so, C ABI in include/tdvc.h) is loaded lazily on the first
 operator call and the load fails loudly when it is missing: there is no CPU or ATen fallback in
@@ -33,7 +35,7 @@ from . import synth  # noqa: F401  (numpy/torch only, no GPU)
 def __getattr__(name):
     # heavy submodules on demand, so that `synth` stays importable without torch.cuda / the .so
     import importlib
-    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', 'wavlm', 'crepe', '_lib'):
+    if name in ('modules', 'losses', 'ops', 'arena', 'train_step', 'parallel', 'hparams', 'util', 'infer', 'ssl_encoder', 'pitch', 'corrupt', 'resample', 'evaluate', 'speaker', 'ecapa', 'wavlm', 'crepe', 'whisper', '_lib'):
         return importlib.import_module(f'{__name__}.{name}')
     if name in ('Generator', 'CollaborativeMultibandDiscriminator', 'ConditionalInstanceNorm', 'LatentClassifier', 'Discriminator'):
         return getattr(importlib.import_module(f'{__name__}.modules'), name)
@@ -55,6 +57,8 @@ def __getattr__(name):
                 'crepe_conv_bwd', 'crepe_head_bwd', 'crepe_frames_bwd', 'crepe_act_mse', 'pack_bwd_weight', 'roll_bins', 'conversion_target',
                 'activation_mse'):
         return getattr(importlib.import_module(f'{__name__}.crepe'), name)
+    if name in ('Whisper', 'WhisperConfig', 'load_whisper', 'whisper_log_mel', 'whisper_mel_filters', 'asr_wer', 'asr_cer', 'asr_report'):
+        return getattr(importlib.import_module(f'{__name__}.whisper'), name)
     if name in ('TrainStep', 'StepConfig'):
         return getattr(importlib.import_module(f'{__name__}.train_step'), name)
     raise AttributeError(name)

@@ -86,6 +86,14 @@ class WavlmGemmArgs(C.Structure):
                 ('y', C.c_void_p), ('y_bs', C.c_int64), ('y_ts', C.c_int64)]
 
 
+class WhisperLinearArgs(C.Structure):
+    _fields_ = [('B', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('epilogue', C.c_int32), ('scale_lo', C.c_int32), ('scale_hi', C.c_int32),
+                ('scale', C.c_float), ('x', C.c_void_p), ('x_bs', C.c_int64), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('w', C.c_void_p),
+                ('bias', C.c_void_p), ('res', C.c_void_p), ('r_bs', C.c_int64), ('y', C.c_void_p), ('y_bs', C.c_int64),
+                ('cache_lo', C.c_int32), ('cache_len', C.c_int32), ('pos', C.c_void_p), ('k_cache', C.c_void_p), ('v_cache', C.c_void_p),
+                ('c_bs', C.c_int64)]
+
+
 class CrepeConvArgs(C.Structure):
     _fields_ = [('N', C.c_int32), ('Cin', C.c_int32), ('Cout', C.c_int32), ('Lin', C.c_int32), ('K', C.c_int32), ('stride', C.c_int32),
                 ('reserved0', C.c_int32), ('reserved1', C.c_int32), ('x', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p),
@@ -258,6 +266,15 @@ SIGNATURES = {
     'tdvc_crepe_frames_bwd_workspace': (C.c_size_t, [C.c_int32, C.c_int32]),
     'tdvc_crepe_frames_bwd': (_i, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp, C.c_size_t, _vp]),
     'tdvc_roll_bins': (_i, [_vp, _i64, _i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    'tdvc_whisper_log_mel_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'tdvc_whisper_log_mel': (_i, [_vp, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _i64, _i64, _i64, _vp, C.c_size_t, _vp]),
+    'tdvc_whisper_attention': (_i, [_vp, _vp, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _i64, _vp]),
+    'tdvc_whisper_embed': (_i, [_vp, _i64, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
+    'tdvc_whisper_linear_step': (_i, [C.POINTER(WhisperLinearArgs), _vp]),
+    'tdvc_whisper_attn_step': (_i, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
+    'tdvc_whisper_workspace': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    'tdvc_whisper_logits': (_i, [_vp, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _i64, _vp, C.c_size_t, _vp]),
+    'tdvc_whisper_pick': (_i, [_vp, C.c_size_t, C.c_int32, C.c_int32, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     'tdvc_contrastive_fwd_bwd': (_i,[_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'tdvc_last_error': (C.c_char_p, []),
     'tdvc_version': (_i, []),
