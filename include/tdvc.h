@@ -149,7 +149,7 @@ void tdvc_fold_reset(void* stream);
 void tdvc_set_force_generic(int on);
 void tdvc_debug_force_tile(int cfg);
 void tdvc_debug_force_gemm_tile(int cfg);
-void tdvc_debug_knob(int which, int value); /* tuning knobs for A/B measurements: 0 = XCD-aware block order of the lean conv kernel (1 = on; default 0: measured null on this path); 3 = one block per CU in the fused conditioning backward (diagnostic); 4 = 1: no sample folding of short sequences (T = 16 / 32) in the lean conv kernel; 5 = 1: exact-fp32 MFMA instead of the split-bf16 x6 weight-grad kernel (conv_wgrad_x6.hip); 6 = 1: tdvc_conv_fwd_x6 always answers TDVC_EUNSUPPORTED; 7 = 1: two instead of three resident blocks per CU in the x6 weight-grad's plan; 8 = 1 (test-only): the 16 x 64 and 32 x 64 tiles of the lean conv kernel run their one-step-ahead MFMA loop instead of the per-tap fragment ring (same bits); 9 = 1 (test-only): the lean conv kernel runs the epilogue that loads, computes and stores one float4 at a time instead of the batched one (same bits) */
+void tdvc_debug_knob(int which, int value); /* tuning knobs for A/B measurements: 0 = XCD-aware block order of the lean conv kernel (1 = on; default 0: measured null on this path); 3 = one block per CU in the fused conditioning backward (diagnostic); 4 = 1: no sample folding of short sequences (T = 16 / 32) in the lean conv kernel; 5 = 1: exact-fp32 MFMA instead of the split-bf16 x6 weight-grad kernel (conv_wgrad_x6.hip); 6 = 1: tdvc_conv_fwd_x6 always answers TDVC_EUNSUPPORTED; 7 = 1: two instead of three resident blocks per CU in the x6 weight-grad's plan; 8 = 1 (test-only): the 16 x 64 and 32 x 64 tiles of the lean conv kernel run their one-step-ahead MFMA loop instead of the per-tap fragment ring (same bits); 9 = 1 (test-only): the lean conv kernel runs the epilogue that loads, computes and stores one float4 at a time instead of the batched one (same bits); 10 = 1 (test-only): the reflect fold of the lean conv kernel's input-grad runs every tap, and every sub-tile on the 16-row tiles, instead of the live ones only (same bits) */
 void tdvc_debug_lds_cap(int bytes);   /* tuning knob: LDS bytes per block the lean kernel's chunk-size choice may use (0 = built-in) */
 void tdvc_debug_trace(int on);
 size_t tdvc_debug_trace_dump(char* buf, size_t cap);

@@ -27,9 +27,10 @@ extern int g_force_tile;
 extern int g_force_gemm_tile;   // conv_mfma.hip: tests pin the tile of the generic MFMA conv kernel
 extern int g_force_generic;      // conv_api.hip: tests route every conv to the scalar kernels
 extern int g_lds_cap;
-extern int g_knob[10];   // tuning knobs (tdvc_debug_knob): [0] XCD-aware block order of the lean conv kernel (default off: measured null, profiles/r02_e_xcd_remap_ab.txt);
+extern int g_knob[11];   // tuning knobs (tdvc_debug_knob): [0] XCD-aware block order of the lean conv kernel (default off: measured null, profiles/r02_e_xcd_remap_ab.txt);
                         // [8] test-only: the lean conv tiles with a fragment ring run their one-step-ahead loop instead (conv_lean.hip)
                         // [9] test-only: the lean conv kernel runs its one-float4-at-a-time epilogue instead of the batched one (conv_lean.hip)
+                        // [10] test-only: the lean conv kernel's reflect fold runs every tap, and every sub-tile on the 16-row tiles, not the live ones only (conv_lean.hip)
 void trace_kernel(const void* fn);
 }
 #define TDVC_TRACE(k) do { if (tdvc::g_trace_on) tdvc::trace_kernel(reinterpret_cast<const void*>(k)); } while (0)

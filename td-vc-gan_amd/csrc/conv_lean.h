@@ -23,6 +23,7 @@ struct LeanP {
   int swz;                             // XCD-aware block order (see conv_lean_kernel)
   int one_ahead;                       // test-only: the ring tiles run their one-step-ahead MFMA loop (see lean_ring_depth)
   int old_epi;                         // test-only: the epilogue handles one float4 at a time, each load behind its own test (see the kernel's epilogue)
+  int full_fold;                       // test-only: the reflect fold runs every tap and, on the 16-row tiles, every sub-tile (see the kernel's fold_taps)
   int fold, seg, Bn;                   // FOLD: samples per 64-column tile, LDS columns per sample segment, batch size
   int vec;                             // host-checked: T % 4 == 0, every pointer 16-byte aligned, batch strides % 4 == 0
   float slope, in_scale, out_scale, add_scale, m_slope;

@@ -427,7 +427,39 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
       }
     }
 
-    if (M_REP >= 2 && (needL || needR)) {   // reflect-pad fold (input-grad of a reflect conv): edge waves only
+    // Reflect-pad fold (input-grad of a reflect conv), edge waves only: the gradient of the mirrored halo columns is added to the
+    // columns they mirror. At tap j the mirrored column u reads the staged tile at position base - u + j * d, base = -pad on the left
+    // side and 2 (T - 1) - pad on the right; a position outside [0, T) holds the zeros the staging wrote. fold_taps gives, for the
+    // 16-column sub-tile that starts at column ca, the taps [jlo, jhi] at which some mirrored column [ua, ub] of the sub-tile reads
+    // inside the sequence (j * d >= ua - base for the first, j * d <= T - 1 - base + ub for the last; with 'same' padding at most
+    // (K - 1) / 2 of the K taps, and 2 of 11 on the second sub-tile of K = 11, d = 5), and false when the sub-tile holds no mirrored
+    // column or no such tap. The loops below run over these taps only: the steps they leave out added zero products to sums that
+    // started at +0 and so never hold -0, and no bit moves. Wave-uniform, kept in scalar registers (the divisions are exact in fp32: numerators <= K * d).
+    // The range is worked out where it is used, per chunk: it depends on nothing the chunk loop changes, and hoisted in front of the
+    // main loop the ranges of every (side, sub-tile) cost the tiles that sit at their register limit scratch or a resident block
+    // (the empty asm keeps the sub-tile's column, and all that follows from it, inside the loop).
+    // p.full_fold (test-only, tdvc_debug_knob 10): every tap, and on the 16-row tiles every sub-tile -- the fold as it was.
+    auto fold_taps = [&](const int side, const int n, int& ca, int& jlo, int& jhi) __attribute__((always_inline)) -> bool {
+      ca = __builtin_amdgcn_readfirstlane(n0 + wcol0 + n * 16);
+      int dd = p.d;
+      asm volatile("" : "+s"(ca), "+s"(dd));
+      const float inv_d = 1.0f / (float)dd;
+      const int cb = ca + 15;
+      int ua, ub, base;
+      if (side == 0) { ua = max(ca, 1); ub = min(min(cb, p.mirror), p.T - 1); base = -p.pad; }
+      else { ua = max(max(ca, p.T - 1 - p.mirror), 0); ub = min(cb, p.T - 2); base = 2 * (p.T - 1) - p.pad; }
+      const int nlo = ua - base, nhi = p.T - 1 - base + ub, kd = (p.K - 1) * dd;
+      int lo = nlo <= 0 ? 0 : (int)(((float)(min(nlo, kd + dd) + dd - 1) + 0.5f) * inv_d);
+      int hi = nhi < 0 ? -1 : (int)(((float)min(nhi, kd) + 0.5f) * inv_d);
+      bool use = ua <= ub && lo <= hi;
+      if (p.full_fold) {
+        use = M_REP == 1 || (side == 0 ? (ca <= p.mirror && cb >= 1) : (ca <= p.T - 2 && cb >= p.T - 1 - p.mirror));
+        lo = 0; hi = p.K - 1;
+      }
+      jlo = __builtin_amdgcn_readfirstlane(lo); jhi = __builtin_amdgcn_readfirstlane(hi);
+      return __builtin_amdgcn_readfirstlane((int)use) != 0;
+    };
+    if (M_REP >= 2 && (needL || needR)) {
       // Per side, only the 16-column sub-tiles that hold mirrored columns take part (pad <= 25: one or two of them). Each
       // runs a software-pipelined (tap, channel-group) loop into a temporary accumulator that is then added to the
       // sub-tile's own accumulators, so the extra work of the blocks at the sequence ends stays a fraction of a chunk.
@@ -435,9 +467,8 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
         if (side == 0 ? !needL : !needR) continue;
 #pragma unroll
         for (int n = 0; n < N_REP; ++n) {
-          const int ca = n0 + wcol0 + n * 16, cb = ca + 15;
-          const int use = __builtin_amdgcn_readfirstlane(side == 0 ? (ca <= p.mirror && cb >= 1) : (ca <= p.T - 2 && cb >= p.T - 1 - p.mirror));
-          if (!use) continue;
+          int ca, jlo, jhi;
+          if (!fold_taps(side, n, ca, jlo, jhi)) continue;
           const int u = ca + ln;
           bool mv; int mb;
           if (side == 0) { mv = (u >= 1 && u <= p.mirror && u < p.T); mb = -u - n0 + p.i0; }
@@ -445,9 +476,9 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
           f32x4 tacc[M_REP];
 #pragma unroll
           for (int m = 0; m < M_REP; ++m) tacc[m] = (f32x4){0.f, 0.f, 0.f, 0.f};
-          const int nit = p.K * csteps;
+          const int nit = (jhi - jlo + 1) * csteps;
           float wq[2][M_REP], xq[2];
-          int mj = 0, mcs = 0;
+          int mj = jlo, mcs = 0;
           auto mload = [&](int buf) {
             const float* wj = w_lane + (p.flip ? p.K - 1 - mj : mj) + mcs * 4 * p.K;
 #pragma unroll
@@ -474,65 +505,53 @@ __global__ __launch_bounds__(256, lean_min_blocks(M_REP, N_REP, WM, XFK)) void c
         }
       }
     }
-    if (M_REP == 1 && (needL || needR)) {   // reflect-pad fold, 16-row tiles: every sub-tile of the wave, straight into its accumulators
+    if (M_REP == 1 && (needL || needR)) {   // reflect-pad fold, 16-row tiles: sub-tile by sub-tile, straight into its accumulators
       for (int side = 0; side < 2; ++side) {
         if (side == 0 ? !needL : !needR) continue;
-        int mb[N_REP]; bool mv[N_REP];
 #pragma unroll
         for (int n = 0; n < N_REP; ++n) {
-          const int u = n0 + wcol0 + n * 16 + ln;
-          if (side == 0) { mv[n] = (u >= 1 && u <= p.mirror && u < p.T); mb[n] = -u - n0 + p.i0; }
-          else { mv[n] = (u >= p.T - 1 - p.mirror && u <= p.T - 2 && u >= 0); mb[n] = 2 * (p.T - 1) - u - n0 + p.i0; }
-        }
-        if constexpr (DEPTH > 0) {
-          if (!p.one_ahead) {   // a ring per tap here too: the clamped column and the lanes' `ok` are the tap's
-            int mbv[N_REP];                                  // lanes without a mirrored column: an origin no tap brings into [0, span)
+          int ca, jlo, jhi;
+          if (!fold_taps(side, n, ca, jlo, jhi)) continue;
+          const int u = ca + ln;
+          bool mv; int mb;
+          if (side == 0) { mv = (u >= 1 && u <= p.mirror && u < p.T); mb = -u - n0 + p.i0; }
+          else { mv = (u >= p.T - 1 - p.mirror && u <= p.T - 2 && u >= 0); mb = 2 * (p.T - 1) - u - n0 + p.i0; }
+          if constexpr (DEPTH > 0) {
+            if (!p.one_ahead) {   // a ring per live tap here too: the clamped column and the lanes' `ok` are the tap's
+              const int mbv = mv ? mb : -(1 << 28);            // lanes without a mirrored column: an origin no tap brings into [0, span)
+              for (int j = jlo; j <= jhi; ++j) {
+                const float* wp = w_lane + (p.flip ? p.K - 1 - j : j);
+                const int idx = mbv + j * p.d;
+                const bool ok = (unsigned)idx < (unsigned)p.span;
+                const float* xp = xs + kq * p.XS + (ok ? idx : 0);
+                ring_run(csteps, [&](int slot) {
 #pragma unroll
-            for (int n = 0; n < N_REP; ++n) mbv[n] = mv[n] ? mb[n] : -(1 << 28);
-            for (int j = 0; j < p.K; ++j) {
-              const float* wp = w_lane + (p.flip ? p.K - 1 - j : j);
-              const float* xp[N_REP]; bool ok[N_REP];
+                  for (int m = 0; m < M_REP; ++m) wv[slot][m] = wp[m * wrep];
+                  xv[slot][n] = *xp; xp += 4 * p.XS;
+                  wp += 4 * p.K;
+                }, [&](int slot) {
 #pragma unroll
-              for (int n = 0; n < N_REP; ++n) {
-                const int idx = mbv[n] + j * p.d;
-                ok[n] = (unsigned)idx < (unsigned)p.span;
-                xp[n] = xs + kq * p.XS + (ok[n] ? idx : 0);
+                  for (int m = 0; m < M_REP; ++m)
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(ok ? xv[slot][n] : 0.f, wv[slot][m], acc[m][n], 0, 0, 0);
+                });
               }
-              ring_run(csteps, [&](int slot) {
-#pragma unroll
-                for (int m = 0; m < M_REP; ++m) wv[slot][m] = wp[m * wrep];
-#pragma unroll
-                for (int n = 0; n < N_REP; ++n) { xv[slot][n] = *xp[n]; xp[n] += 4 * p.XS; }
-                wp += 4 * p.K;
-              }, [&](int slot) {
-#pragma unroll
-                for (int m = 0; m < M_REP; ++m)
-#pragma unroll
-                  for (int n = 0; n < N_REP; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(ok[n] ? xv[slot][n] : 0.f, wv[slot][m], acc[m][n], 0, 0, 0);
-              });
+              continue;
             }
-            continue;
           }
-        }
-        for (int j = 0; j < p.K; ++j) {   // plain loop (from four MFMAs per step on; test-only for the ring's tiles)
-          const float* wj = w_lane + (p.flip ? p.K - 1 - j : j);
-          for (int cs = 0; cs < csteps; ++cs) {
-            float wm_[M_REP], xm_[N_REP];
+          for (int j = jlo; j <= jhi; ++j) {   // plain loop (from four MFMAs per step on; test-only for the ring's tiles)
+            const float* wj = w_lane + (p.flip ? p.K - 1 - j : j);
+            const int idx = mb + j * p.d;
+            const bool ok = mv && idx >= 0 && idx < p.span;
+            for (int cs = 0; cs < csteps; ++cs) {
+              float wm_[M_REP];
 #pragma unroll
-            for (int m = 0; m < M_REP; ++m) wm_[m] = wj[m * 16 * p.WS + cs * 4 * p.K];
-#pragma unroll
-            for (int n = 0; n < N_REP; ++n) {
-              const int idx = mb[n] + j * p.d;
-              const bool ok = mv[n] && idx >= 0 && idx < p.span;
+              for (int m = 0; m < M_REP; ++m) wm_[m] = wj[m * 16 * p.WS + cs * 4 * p.K];
               const float t = xs[(cs * 4 + kq) * p.XS + (ok ? idx : 0)];
-              xm_[n] = ok ? t : 0.f;
+              const float xm_ = ok ? t : 0.f;
+#pragma unroll
+              for (int m = 0; m < M_REP; ++m)
+                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(xm_, wm_[m], acc[m][n], 0, 0, 0);
             }
-#pragma unroll
-            for (int m = 0; m < M_REP; ++m)
-#pragma unroll
-              for (int n = 0; n < N_REP; ++n)
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(xm_[n], wm_[m], acc[m][n], 0, 0, 0);
           }
         }
       }
@@ -870,6 +889,7 @@ static hipError_t lean_launch3(const LeanP& p, int B, hipStream_t st) {
   LeanP q = p; q.swz = g_knob[0] && (long)grid.x * grid.y * grid.z >= 16;
   q.one_ahead = g_knob[8] != 0;
   q.old_epi = g_knob[9] != 0;
+  q.full_fold = g_knob[10] != 0;
   const size_t lds = (size_t)(p.xnp * p.xrp * p.XS + p.wnp * p.wrp * p.WS) * sizeof(float);
   hipLaunchKernelGGL(k, grid, dim3(256), lds, st, q);
   return hipGetLastError();

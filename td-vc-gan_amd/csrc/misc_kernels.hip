@@ -30,7 +30,7 @@ int g_trace_on = 0;
 int g_force_tile = -1;
 int g_force_gemm_tile = -1;
 int g_lds_cap = 0;
-int g_knob[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+int g_knob[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static std::mutex g_trace_mu;
 static std::set<std::string> g_trace_names;
 void trace_kernel(const void* fn) {
@@ -51,7 +51,7 @@ void trace_kernel(const void* fn) {
 extern "C" void tdvc_debug_force_tile(int cfg) { tdvc::g_force_tile = cfg; }
 extern "C" void tdvc_debug_force_gemm_tile(int cfg) { tdvc::g_force_gemm_tile = cfg; }
 extern "C" void tdvc_debug_lds_cap(int bytes) { tdvc::g_lds_cap = bytes; }
-extern "C" void tdvc_debug_knob(int which, int value) { if (which >= 0 && which < 10) tdvc::g_knob[which] = value; }
+extern "C" void tdvc_debug_knob(int which, int value) { if (which >= 0 && which < 11) tdvc::g_knob[which] = value; }
 namespace tdvc {
 __global__ __launch_bounds__(256) void poison_lds_kernel(unsigned word, int nwords, unsigned* sink) {
   extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -25,6 +25,7 @@ SHAPES = {  # name: (cin, cout, k, dil, T, reflect, pre)
     'cond2_c16': (136, 32, 3, 1, 16000, False, 1), 'cond2_c32': (136, 64, 3, 1, 8000, False, 1), 'cond2_c64': (136, 128, 3, 1, 4000, False, 1),
     'd5': (1024, 1024, 5, 1, 63, False, 0), 'd5_T32': (1024, 1024, 5, 1, 32, False, 0), 'head1024': (1024, 16, 3, 1, 63, False, 0),
     'mrf256k7': (256, 256, 7, 1, 50, True, 1), 'c128k11d5': (128, 128, 11, 5, 500, True, 1), 'cond2_c64s': (136, 128, 3, 1, 1024, False, 1), 'cond2_c64m': (136, 128, 3, 1, 2048, False, 1),
+    'c64k11d5': (64, 64, 11, 5, 4000, True, 1), 'c32k11d5': (32, 32, 11, 5, 8000, True, 1), 'mrf256k11': (256, 256, 11, 1, 50, True, 1),
 }
 NAMES = ['prologue', 'bar_top', 'commit', 'bar_staged', 'issue', 'mfma', 'epilogue']
 
